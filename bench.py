@@ -30,6 +30,9 @@ Rank 0 prints one JSON line: LR Mpixels/s over all GPUs, plus
                    this command (profiles/r*_pmc_per_dispatch.json): PMC counters cannot be read in-process.
   cpu_baseline  -- the float32 torch-CPU restatement of the same graph (oracle/cpu_path_torch.py;
                    TensorFlow is not installable) timed on the host cores on a bounded sample.
+
+``--dump-outputs DIR`` writes the y of the last timed step to DIR as .npy (inputs and weights are seeded: the same arguments
+give the same inputs), so that two builds can be compared output for output.
 """
 
 import argparse
@@ -402,7 +405,44 @@ def parse_args():
     ap.add_argument("--check-output", action="store_true",
                     help="after the timed steps, hash every output patch (sha256) and report the digest of the global batch "
                          "in patch order: equal for any number of ranks with --strong (tests/test_multi_rank_gpu.py)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the output y of the last timed step to DIR/y.npy (DIR/y_rank<r>.npy with "
+                         "N > 1), float32 as the engine returns it; a fixed seeded sample of patches (indices in DIR/y_patches.npy) "
+                         "when the whole output exceeds %d MB over all ranks" % (DUMP_BUDGET_BYTES // 10**6))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6     # --dump-outputs: bytes written over all ranks, npy headers included
+
+
+def dump_selection(n, patch_bytes, budget):
+    """Patches of one rank's output that --dump-outputs writes: None (all n) when they fit in `budget` bytes, else a fixed
+    seeded sample, sorted, sized so that the patches plus their float64 indices and two npy headers fit."""
+    if n * patch_bytes + 256 <= budget:
+        return None
+    k = max(0, min(n, (budget - 512) // (patch_bytes + 8)))
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(dirname, y, rank, world):
+    """--dump-outputs: this rank's y (n, H, W, 1) float32 as <dirname>/y.npy (y_rank<r>.npy with N > 1), whole or sampled."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    stem = "y" if world == 1 else "y_rank%d" % rank
+    n = y.shape[0]
+    sel = dump_selection(n, y[0].numel() * y.element_size() if n else 0, DUMP_BUDGET_BYTES // world)
+    files = [stem + ".npy"]
+    if sel is None:
+        arr = y.cpu().numpy()
+    else:
+        arr = y[torch.from_numpy(sel).to(y.device)].cpu().numpy()
+        files.append(stem + "_patches.npy")
+        np.save(os.path.join(dirname, files[1]), sel.astype(np.float64))
+    np.save(os.path.join(dirname, files[0]), arr.astype(np.float32, copy=False))
+    return {"dir": dirname, "files": files, "patches": int(arr.shape[0]), "of_patches": int(n), "sampled": sel is not None}
 
 
 def main():
@@ -496,6 +536,8 @@ def main():
     per_op_ms = eng.profile(with_float32_plan=True)         # averaged over the timed steps
     f32_plan_ms = per_op_ms.pop()     # the gated float32 launches behind the pass (empty unless an image left the f16 range)
     eng.set_option("profile", 0)
+    # the last timed step's y, before any leg below writes y again
+    dumped = dump_outputs(args.dump_outputs, y, rank, world) if args.dump_outputs else None
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if share_gpu else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -654,6 +696,8 @@ def main():
             result["strong_scaling"] = strong_leg
         if digest is not None:
             result["output_sha256"] = digest
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if north_star:
             result["north_star"] = north_star
         if world == 1 and not args.no_cpu_baseline:

@@ -281,9 +281,11 @@ def test_filter_schedule_matches_python_for_many_flags(oracle):
 def test_no_cpu_fallback():
     """Without a HIP device the product path must fail loudly, never compute on the CPU."""
     import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is present")
     from dcscn_amd import engine
+    # the library's own HIP runtime is asked too: in the whole suite the library is loaded before torch, whose wheel then brings a
+    # second HIP runtime that reports no device (see _Hip in test_hip_parity.py), so torch alone says "no GPU" on a GPU machine
+    if torch.cuda.is_available() or engine.device_count() > 0:
+        pytest.skip("a GPU is present")
     with pytest.raises(engine.EngineError) as e:
         engine.Engine(dict())
     assert e.value.status == 5
