@@ -156,6 +156,39 @@ int dcscn_set_tensor(dcscn_handle h, const char* name, const float* data, const 
     return DCSCN_OK;
 }
 
+// finalize_op over the plan; the device images it makes are kept apart (pack_allocs) so that repack_weights can replace them
+static int pack_ops(dcscn_ctx* h) {
+    const size_t first = h->device_allocs.size();
+    int rc = DCSCN_OK;
+    for (Op& op : h->ops) {
+        rc = finalize_op(h, op);
+        if (rc) break;
+    }
+    h->pack_allocs.insert(h->pack_allocs.end(), h->device_allocs.begin() + first, h->device_allocs.end());
+    h->device_allocs.resize(first);
+    return rc;
+}
+
+}  // extern "C"
+
+namespace dcscn_impl {
+// The host copies of the variables changed (training): pack the same plan again from them.
+int repack_weights(dcscn_ctx* h) {
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (h->graph_exec) {
+        (void)hipGraphExecDestroy(h->graph_exec);
+        h->graph_exec = nullptr;
+        h->graph_key = dcscn_ctx::GraphKey();
+    }
+    h->graph_seen = dcscn_ctx::GraphKey();
+    for (void* p : h->pack_allocs) (void)hipFree(p);
+    h->pack_allocs.clear();
+    return pack_ops(h);
+}
+}  // namespace dcscn_impl
+
+extern "C" {
+
 int dcscn_finalize(dcscn_handle h) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (h->finalized) return DCSCN_OK;
@@ -168,10 +201,8 @@ int dcscn_finalize(dcscn_handle h) {
     densify_features(h);
     fuse_feat3_stream(h);
     fold_whole_tail(h);                         // x3 / x4: whatever tail the rewrites above left becomes the float32 plan of ONE folded launch
-    for (Op& op : h->ops) {
-        int rc = finalize_op(h, op);
-        if (rc) return rc;
-    }
+    int rc0 = pack_ops(h);
+    if (rc0) return rc0;
     plan_p16(h);
     for (Op& op : h->ops) {
         int rc = DCSCN_OK;
@@ -361,6 +392,8 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
 
 int dcscn_forward_device(dcscn_handle h, const float* x, const float* x2, float* y, int n, int height, int width, void* stream) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (h->finalized)
+        if (int rc_ = train_sync_inference(h)) return rc_;
     return run_forward(h, x, x2, y, n, height, width, stream ? (hipStream_t)stream : h->stream);
 }
 
@@ -433,6 +466,7 @@ static int forward_host_chunked(dcscn_ctx* h, const float* x, const float* x2, f
 int dcscn_forward(dcscn_handle h, const float* x, const float* x2, float* y, int n, int height, int width) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_forward before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
     if (n < 0 || height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape n=%d h=%d w=%d", n, height, width);
     if (n == 0) return DCSCN_OK;
     if (!x || !x2 || !y) return fail(h, DCSCN_ERR_INVALID_ARG, "null image pointer");
@@ -495,6 +529,7 @@ int dcscn_resize_bicubic_device(dcscn_handle h, const float* in, float* out, int
 int dcscn_forward_lr(dcscn_handle h, const float* x, float* y, int n, int height, int width) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_forward_lr before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
     if (n < 0 || height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape n=%d h=%d w=%d", n, height, width);
     if (n == 0) return DCSCN_OK;
     if (!x || !y) return fail(h, DCSCN_ERR_INVALID_ARG, "null image pointer");
@@ -528,6 +563,7 @@ static int ensemble_on_device(dcscn_ctx* h, int height, int width, int n) {
 int dcscn_forward_ensemble(dcscn_handle h, const float* x, const float* x2, double* y, int height, int width, int n_ensemble) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_forward_ensemble before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
     if (!x || !x2 || !y) return fail(h, DCSCN_ERR_INVALID_ARG, "null image pointer");
     if (n_ensemble < 1 || n_ensemble > 8) return fail(h, DCSCN_ERR_INVALID_ARG, "n_ensemble %d outside [1, 8]", n_ensemble);
     if (height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape h=%d w=%d", height, width);
@@ -627,6 +663,7 @@ static int download_sr(dcscn_ctx* h, size_t hr, int n_ensemble, double* y) {
 int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, double* true_y, float* lr, double* y) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_evaluate_rgb before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
     if (!rgb || !y) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_evaluate_rgb: null pointer");
     if (n_ensemble < 1 || n_ensemble > 8) return fail(h, DCSCN_ERR_INVALID_ARG, "n_ensemble %d outside [1, 8]", n_ensemble);
     const int s = h->cfg.scale;
@@ -655,6 +692,7 @@ int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width
 int dcscn_sr_rgb(dcscn_handle h, const uint8_t* rgb, const uint8_t* rgb_upscaled, int height, int width, int n_ensemble, double* y, double* rgb_out) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_sr_rgb before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
     if (!rgb || !rgb_upscaled || !rgb_out) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_sr_rgb: null pointer");
     if (n_ensemble < 1 || n_ensemble > 8) return fail(h, DCSCN_ERR_INVALID_ARG, "n_ensemble %d outside [1, 8]", n_ensemble);
     if (height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape h=%d w=%d", height, width);
@@ -753,7 +791,9 @@ int dcscn_destroy(dcscn_handle h) {
     if (h->done_ev) (void)hipEventDestroy(h->done_ev);
     for (hipEvent_t e : h->host_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    train_free(h);
     for (void* p : h->device_allocs) (void)hipFree(p);
+    for (void* p : h->pack_allocs) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);
     if (h->d_zrec) (void)hipFree(h->d_zrec);
     if (h->d_digest) (void)hipFree(h->d_digest);

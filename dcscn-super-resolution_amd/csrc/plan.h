@@ -58,6 +58,8 @@ struct ColSeg {
                                       // pointwise weights when they are packed: sum_c (x_c d_c) p_co = sum_c x_c (d_c p_co)
 };
 
+struct TrainState;   // train.hip
+
 struct Op {
     OpKind kind = OP_CONV;
     std::string name;
@@ -228,6 +230,8 @@ struct dcscn_ctx {
     std::vector<int> ev_op;                  // launch index of each recorded pair (ops.size() = the float32 plan behind a pass)
     int ev_forwards = 0;                     // forwards recorded since the last dcscn_get_profile
     std::vector<double> prof_ms;
+    std::vector<void*> pack_allocs;          // device images finalize_op made (freed and rebuilt when training changed the variables)
+    dcscn_impl::TrainState* train = nullptr;      // train.hip: the training plan, variables and slots (dcscn_train_begin)
 };
 
 namespace dcscn_impl {
@@ -272,6 +276,11 @@ int pack_feat_stream(dcscn_ctx* h, Op& op);
 int pack_tail_stream(dcscn_ctx* h, Op& op);
 int pack_feat3_stream(dcscn_ctx* h, Op& op);
 int pack_foldx(dcscn_ctx* h, Op& op);
+// api.hip
+int repack_weights(dcscn_ctx* h);
+// train.hip
+void train_free(dcscn_ctx* h);
+int train_sync_inference(dcscn_ctx* h);
 // exec.hip
 int ensure_workspace(dcscn_ctx* h, int nb, int H, int W, hipStream_t stream);
 // redo = false: the launch of the pass (split16 kernels where the handle's options allow); true: the op's float32 launch gated by the

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 MAX_NAME = 128
 
 ACTIVATORS = {None: 0, "": 0, "none": 0, "prelu": 1, "relu": 2, "leaky_relu": 3, "sigmoid": 4, "tanh": 5, "selu": 6}
@@ -28,7 +28,12 @@ EXPORTED_SYMBOLS = (
     "dcscn_last_error", "dcscn_destroy", "dcscn_resize_bicubic", "dcscn_resize_bicubic_device", "dcscn_forward_lr",
     "dcscn_resample_table", "dcscn_get_stream", "dcscn_synchronize", "dcscn_convert_rgb_to_y", "dcscn_convert_rgb_to_ycbcr",
     "dcscn_convert_y_and_cbcr_to_rgb", "dcscn_evaluate_rgb", "dcscn_sr_rgb",
+    "dcscn_train_begin", "dcscn_train_step", "dcscn_train_step_device", "dcscn_train_gradients", "dcscn_get_tensor",
+    "dcscn_set_train_tensor",
 )
+
+# dcscn_optimizer; the names of helper/args.py --optimizer
+OPTIMIZERS = {"adam": 0, "gd": 1, "momentum": 2, "adadelta": 3, "adagrad": 4, "rmsprop": 5}
 
 
 class EngineError(RuntimeError):
@@ -59,6 +64,23 @@ class Config(ctypes.Structure):
         ("channels", ctypes.c_int32),
         ("legacy_no_c", ctypes.c_int32),
         ("batch_norm", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 8),
+    ]
+
+
+class TrainConfig(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_int32),
+        ("optimizer", ctypes.c_int32),
+        ("use_l1_loss", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("epsilon", ctypes.c_double),
+        ("momentum", ctypes.c_double),
+        ("l2_decay", ctypes.c_double),
+        ("clipping_norm", ctypes.c_double),
+        ("keep_prob", ctypes.c_double),
         ("reserved", ctypes.c_int32 * 8),
     ]
 
@@ -154,6 +176,12 @@ def load_library():
     lib.dcscn_last_error.argtypes = [vp]
     lib.dcscn_last_error.restype = c.c_char_p
     lib.dcscn_destroy.argtypes = [vp]
+    lib.dcscn_train_begin.argtypes = [vp, c.POINTER(TrainConfig)]
+    lib.dcscn_train_step.argtypes = [vp, fp, fp, fp, c.c_int, c.c_int, c.c_int, c.c_double, c.c_uint64, dp]
+    lib.dcscn_train_step_device.argtypes = [vp, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_double, c.c_uint64, dp, vp]
+    lib.dcscn_train_gradients.argtypes = [vp, fp, fp, fp, c.c_int, c.c_int, c.c_int, c.c_uint64, dp]
+    lib.dcscn_get_tensor.argtypes = [vp, c.c_char_p, fp, c.c_int64]
+    lib.dcscn_set_train_tensor.argtypes = [vp, c.c_char_p, fp, c.c_int64]
     if lib.dcscn_abi_version() != ABI_VERSION:
         raise EngineError(5, "ABI mismatch: library %d, binding %d" % (lib.dcscn_abi_version(), ABI_VERSION))
     _lib = lib
@@ -199,6 +227,26 @@ def make_config(cfg):
     c.channels = int(get("channels", 1))
     c.legacy_no_c = int(bool(get("legacy_no_c", False)))
     c.batch_norm = int(bool(get("batch_norm", False)))
+    return c
+
+
+def make_train_config(flags):
+    """Translate the training flags of helper/args.py (dict or object) into the C struct."""
+    get = flags.get if isinstance(flags, dict) else (lambda k, d=None: getattr(flags, k, d))
+    opt = get("optimizer", "adam")
+    if opt not in OPTIMIZERS:
+        raise EngineError(1, "unknown optimizer '%s'" % opt)
+    c = TrainConfig()
+    c.struct_size = ctypes.sizeof(TrainConfig)
+    c.optimizer = OPTIMIZERS[opt]
+    c.use_l1_loss = int(bool(get("use_l1_loss", False)))
+    c.beta1 = float(get("beta1", 0.9))
+    c.beta2 = float(get("beta2", 0.999))
+    c.epsilon = float(get("epsilon", 1e-8))
+    c.momentum = float(get("momentum", 0.9))
+    c.l2_decay = float(get("l2_decay", 0.0001))
+    c.clipping_norm = float(get("clipping_norm", 5))
+    c.keep_prob = float(get("dropout_rate", 0.8))
     return c
 
 
@@ -399,6 +447,77 @@ class Engine:
         self._check(self._lib.dcscn_forward_device(self._h, ctypes.c_void_p(x_ptr), ctypes.c_void_p(x2_ptr),
                                                    ctypes.c_void_p(y_ptr), n, h, w,
                                                    ctypes.c_void_p(stream) if stream else None))
+
+    # ---- training (DCSCN.py:334-425; "Training" in include/dcscn.h) ----
+    def train_begin(self, flags):
+        """build_optimizer: ``flags`` holds the training flags of helper/args.py (optimizer, beta1, beta2, epsilon, momentum,
+        l2_decay, clipping_norm, dropout_rate = keep probability, use_l1_loss)."""
+        c = make_train_config(flags)
+        self._check(self._lib.dcscn_train_begin(self._h, ctypes.byref(c)))
+        self.training = True
+
+    def _train_arrays(self, x, x2, y_true):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n, h, w = x.shape[0], x.shape[1], x.shape[2]
+        s = self.scale
+        x2 = np.ascontiguousarray(x2, dtype=np.float32)
+        y_true = np.ascontiguousarray(y_true, dtype=np.float32)
+        if x.size != n * h * w or x2.size != n * h * w * s * s or y_true.size != n * h * w * s * s:
+            raise EngineError(4, "x %s, x2 %s, y_true %s do not match a [n, h, w] / [n, %dh, %dw] batch" % (x.shape, x2.shape, y_true.shape, s, s))
+        return x, x2, y_true, n, h, w
+
+    def train_step(self, x, x2, y_true, lr, dropout_key=0):
+        """One optimizer step on host arrays; returns (image_loss, mse, gradient norm before clipping, total loss)."""
+        x, x2, y_true, n, h, w = self._train_arrays(x, x2, y_true)
+        fp = ctypes.POINTER(ctypes.c_float)
+        stats = (ctypes.c_double * 4)()
+        self._check(self._lib.dcscn_train_step(self._h, x.ctypes.data_as(fp), x2.ctypes.data_as(fp), y_true.ctypes.data_as(fp),
+                                               n, h, w, float(lr), int(dropout_key) & (2 ** 64 - 1), stats))
+        return tuple(stats)
+
+    def train_gradients(self, x, x2, y_true, dropout_key=0):
+        """Forward and backward only; the gradients are then readable as get_tensor("<var>/grad")."""
+        x, x2, y_true, n, h, w = self._train_arrays(x, x2, y_true)
+        fp = ctypes.POINTER(ctypes.c_float)
+        stats = (ctypes.c_double * 4)()
+        self._check(self._lib.dcscn_train_gradients(self._h, x.ctypes.data_as(fp), x2.ctypes.data_as(fp), y_true.ctypes.data_as(fp),
+                                                    n, h, w, int(dropout_key) & (2 ** 64 - 1), stats))
+        return tuple(stats)
+
+    def train_step_device(self, x_ptr, x2_ptr, y_ptr, n, h, w, lr, dropout_key=0, stream=None, want_stats=True):
+        """One step on device pointers (e.g. ``torch.Tensor.data_ptr()``); with want_stats the call synchronises and
+        returns the stats of train_step, otherwise it only enqueues and returns None."""
+        stats = (ctypes.c_double * 4)() if want_stats else None
+        self._check(self._lib.dcscn_train_step_device(self._h, ctypes.c_void_p(x_ptr), ctypes.c_void_p(x2_ptr), ctypes.c_void_p(y_ptr),
+                                                      int(n), int(h), int(w), float(lr), int(dropout_key) & (2 ** 64 - 1), stats,
+                                                      ctypes.c_void_p(stream) if stream else None))
+        return tuple(stats) if want_stats else None
+
+    def _numel(self, name):
+        base = name
+        for suffix in ("/grad", "/Adam_1", "/Adam", "/Momentum"):
+            if name.endswith(suffix):
+                base = name[: -len(suffix)]
+                break
+        if base in ("beta1_power", "beta2_power"):
+            return ()
+        for n, shape in self.tensor_specs():
+            if n == base:
+                return shape
+        raise EngineError(4, "unknown tensor '%s'" % name)
+
+    def get_tensor(self, name):
+        """A variable (the trained value while training), "<var>/grad", a slot ("<var>/Adam", "<var>/Adam_1",
+        "<var>/Momentum") or "beta1_power" / "beta2_power", shaped like the checkpoint variable."""
+        shape = self._numel(name)
+        out = np.empty(shape, np.float32)
+        self._check(self._lib.dcscn_get_tensor(self._h, name.encode(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size))
+        return out
+
+    def set_train_tensor(self, name, array):
+        """Write a variable or an optimizer slot of a training handle (resume)."""
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        self._check(self._lib.dcscn_set_train_tensor(self._h, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size))
 
     # ---- colour path (helper/utilty.py:142-193 and the RGB pipelines of evaluate.py / sr.py on the device) ----
     @staticmethod

@@ -10,13 +10,17 @@ What changes underneath: ``build_graph`` derives the layer list instead of a TF 
 ``load_model`` reads the TF checkpoint without TensorFlow (ckpt.py) and uploads it to the HIP
 engine, and ``do`` calls the C ABI (engine.py) where the reference calls ``sess.run``.  The
 self-ensemble copies run as two device batches instead of eight sequential batch-1 runs.
-Training (train.py, DCSCN.py:334-532) is out of scope.
+Training (train.py, DCSCN.py:334-425, 727-769) runs on the engine's training plan: ``build_optimizer`` records the flags,
+the first ``train_batch`` after ``init_all_variables`` / ``load_model`` starts it (dcscn_train_begin), and
+``save_model`` / ``load_model`` carry the optimizer slots under TF's names once training has begun.
 """
 
 import logging
 import math
 import os
+import shutil
 import sys
+import time
 
 import numpy as np
 
@@ -84,6 +88,42 @@ class SuperResolution:
         self.psnr_calc_border_size = flags.psnr_calc_border_size
         if self.psnr_calc_border_size < 0:
             self.psnr_calc_border_size = self.scale
+
+        # training parameters (DCSCN.py:50-93)
+        fget = lambda k, d: getattr(flags, k, d)
+        self.dropout_rate = fget("dropout_rate", 0.8)
+        self.l2_decay = fget("l2_decay", 0.0001)
+        self.optimizer = fget("optimizer", "adam")
+        self.beta1 = fget("beta1", 0.9)
+        self.beta2 = fget("beta2", 0.999)
+        self.epsilon = fget("epsilon", 1e-8)
+        self.momentum = fget("momentum", 0.9)
+        self.batch_num = fget("batch_num", 20)
+        self.batch_image_size = fget("batch_image_size", 48)
+        self.stride_size = fget("stride_size", 0) or self.batch_image_size // 2
+        self.clipping_norm = fget("clipping_norm", 5)
+        self.use_l1_loss = fget("use_l1_loss", False)
+        self.initial_lr = fget("initial_lr", 0.002)
+        self.lr_decay = fget("lr_decay", 0.5)
+        self.lr_decay_epoch = fget("lr_decay_epoch", 9)
+        self.training_images = int(math.ceil(fget("training_images", 24000) / self.batch_num) * self.batch_num)
+        self.total_epochs = 0
+        lr = self.initial_lr
+        while lr > fget("end_lr", 2e-5):
+            self.total_epochs += self.lr_decay_epoch
+            lr *= self.lr_decay
+        self.log_filename = fget("log_filename", "log.txt")
+        self.train = None
+        self.lr = self.initial_lr
+        self.step = self.training_step = self.epochs_completed = self.epochs_completed_in_stage = 0
+        self.training_loss_sum = self.training_psnr_sum = 0
+        self.start_time = time.time()
+        self.total_time = 0.0
+        # dropout masks: dcscn_train_step's key = dropout_seed * 2^32 + step, so a resumed run given the same step has the same masks
+        self.dropout_seed = 0
+        self._train_flags = None            # build_optimizer
+        self._train_engine = None           # the engine training was begun on
+        self._pending_slots = None          # optimizer slots of a checkpoint loaded before training began
 
         self.name = self.get_model_name(model_name)
 
@@ -184,7 +224,12 @@ class SuperResolution:
             self.features, "{:,}".format(self.complexity), self.receptive_fields))
 
     def build_optimizer(self):
-        """Training-only in the reference (DCSCN.py:334-395); inference needs nothing here."""
+        """DCSCN.py:334-413: loss (mse or l1, + l2_decay * sum of l2_loss over the filters), clip_by_global_norm, and the
+        optimizer of --optimizer.  The engine's training plan is started on the first train_batch, after the variables
+        are initialised or restored; adadelta / adagrad / rmsprop are refused there."""
+        self._train_flags = dict(optimizer=self.optimizer, beta1=self.beta1, beta2=self.beta2, epsilon=self.epsilon,
+                                 momentum=self.momentum, l2_decay=self.l2_decay, clipping_norm=self.clipping_norm,
+                                 dropout_rate=self.dropout_rate, use_l1_loss=self.use_l1_loss)
 
     def build_summary_saver(self, with_saver=True):
         """TensorBoard writers / Saver in the reference (tf_graph.py:298-305); nothing to create."""
@@ -222,8 +267,15 @@ class SuperResolution:
         if not ckpt.has_data(filename):
             print("Error. [%s] has no data shard (.data-00000-of-00001)!" % filename)
             sys.exit(-1)
-        tensors = ckpt.load_checkpoint(filename)
-        self.load_weights(tensors)
+        if self._train_flags is not None:
+            # a training run: the variables and, when the checkpoint has them, the optimizer slots (tf.train.Saver restores both)
+            tensors = ckpt.load_checkpoint(filename, include_optimizer_slots=True)
+            slots = {k: v for k, v in tensors.items() if ckpt.is_optimizer_slot(k)}
+            self.load_weights({k: v for k, v in tensors.items() if k not in slots})
+            self._pending_slots = slots or None
+        else:
+            tensors = ckpt.load_checkpoint(filename)
+            self.load_weights(tensors)
         if output_log:
             logging.info("Model restored [ %s ]." % filename)
         else:
@@ -239,7 +291,10 @@ class SuperResolution:
             filename = self.checkpoint_dir + "/" + name + "_" + str(trial) + ".ckpt"
         else:
             filename = self.checkpoint_dir + "/" + name + ".ckpt"
-        tensors = self._weights if self._weights is not None else self._pending_init
+        if self._training_active():
+            tensors = self._training_tensors()             # the trained variables and the optimizer slots, as TF's Saver writes them
+        else:
+            tensors = self._weights if self._weights is not None else self._pending_init
         if tensors is None:
             self.init_all_variables()
             tensors = self._pending_init
@@ -290,6 +345,154 @@ class SuperResolution:
         if self._engine is not None:
             self._engine.close()
             self._engine = None
+        self._train_engine = None
+
+    # ---- training (DCSCN.py:146-190, 426-532, 727-769) ---------------------------------------------
+    def load_dynamic_datasets(self, data_dir, batch_image_size):
+        """Opens an image directory as a dataset; patches are cut when build_input_batch() is called."""
+        from helper import loader
+        self.train = loader.DynamicDataSets(self.scale, batch_image_size, channels=self.channels,
+                                            resampling_method=self.resampling_method)
+        self.train.set_data_dir(data_dir)
+
+    def load_datasets(self, data_dir, batch_dir, batch_image_size, stride_size=0):
+        """BatchDataSets (--build_batch true) is not supported: train from the image directory (DynamicDataSets)."""
+        print("Error. --build_batch true (BatchDataSets) is not supported; use --build_batch false.")
+        sys.exit(-1)
+
+    def _training_active(self):
+        return self._train_engine is not None and self._train_engine is self._engine
+
+    def _ready_training(self):
+        if self._train_flags is None:
+            raise RuntimeError("train_batch() before build_optimizer()")
+        eng = self._ready_engine()
+        if self._train_engine is not eng:
+            eng.train_begin(self._train_flags)
+            self._train_engine = eng
+            if self._pending_slots:
+                for name, value in self._pending_slots.items():
+                    eng.set_train_tensor(name, value)
+            self._pending_slots = None
+        return eng
+
+    def _training_tensors(self):
+        eng = self._engine
+        names = [n for n, _ in eng.tensor_specs()]
+        tensors = {n: eng.get_tensor(n) for n in names}
+        if self.optimizer == "adam":
+            for n in names:
+                tensors[n + "/Adam"] = eng.get_tensor(n + "/Adam")
+                tensors[n + "/Adam_1"] = eng.get_tensor(n + "/Adam_1")
+            tensors["beta1_power"] = eng.get_tensor("beta1_power")
+            tensors["beta2_power"] = eng.get_tensor("beta2_power")
+        elif self.optimizer == "momentum":
+            for n in names:
+                tensors[n + "/Momentum"] = eng.get_tensor(n + "/Momentum")
+        return tensors
+
+    def init_epoch_index(self):
+        self.batch_input = self.batch_num * [None]
+        self.batch_input_bicubic = self.batch_num * [None]
+        self.batch_true = self.batch_num * [None]
+        self.training_psnr_sum = 0
+        self.training_loss_sum = 0
+        self.training_step = 0
+        self.train.init_batch_index()
+
+    def build_input_batch(self):
+        for i in range(self.batch_num):
+            self.batch_input[i], self.batch_input_bicubic[i], self.batch_true[i] = self.train.load_batch_image(self.max_value)
+
+    def dropout_key(self):
+        return (int(self.dropout_seed) << 32) + int(self.step)
+
+    def train_batch(self):
+        """One optimizer step on the current batch (sess.run(training_optimizer, ...), DCSCN.py:426-436)."""
+        eng = self._ready_training()
+        x = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input])
+        x2 = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input_bicubic])
+        y = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_true])
+        image_loss, mse, _, _ = eng.train_step(x, x2, y, self.lr, dropout_key=self.dropout_key())
+        self.training_loss_sum += image_loss
+        self.training_psnr_sum += 0 if mse == 0 else 20 * math.log(self.max_value / math.sqrt(mse), 10)
+        self.training_step += 1
+        self.step += 1
+
+    def log_to_tensorboard(self, test_filename, psnr, save_meta_data=True):
+        """TensorBoard summaries (DCSCN.py:438-468): not written -- there is no TensorBoard here.  Deliberately a no-op."""
+
+    def update_epoch_and_lr(self):
+        self.epochs_completed_in_stage += 1
+        if self.epochs_completed_in_stage >= self.lr_decay_epoch:
+            self.lr *= self.lr_decay
+            self.epochs_completed_in_stage = 0
+            return True
+        return False
+
+    def init_train_step(self):
+        self.lr = self.initial_lr
+        self.epochs_completed = 0
+        self.epochs_completed_in_stage = 0
+        self.min_validation_mse = -1
+        self.min_validation_epoch = -1
+        self.step = 0
+        self.start_time = time.time()
+
+    def end_train_step(self):
+        self.total_time = time.time() - self.start_time
+
+    def print_status(self, psnr, ssim, log=False):
+        if self.step == 0:
+            logging.info("Initial PSNR:%f SSIM:%f" % (psnr, ssim))
+            return
+        processing_time = (time.time() - self.start_time) / self.step
+        if self.use_l1_loss:
+            line_a = "%s Step:%s PSNR:%f SSIM:%f (Training Loss:%0.3f)" % (
+                util.get_now_date(), "{:,}".format(self.step), psnr, ssim, self.training_loss_sum / max(self.training_step, 1))
+        else:
+            line_a = "%s Step:%s PSNR:%f SSIM:%f (Training PSNR:%0.3f)" % (
+                util.get_now_date(), "{:,}".format(self.step), psnr, ssim, self.training_psnr_sum / max(self.training_step, 1))
+        estimated = processing_time * (self.total_epochs - self.epochs_completed) * (self.training_images // self.batch_num)
+        h = estimated // (60 * 60)
+        estimated -= h * 60 * 60
+        m = estimated // 60
+        s = estimated - m * 60
+        line_b = "Epoch:%d LR:%f (%2.3fsec/step) Estimated:%d:%d:%d" % (self.epochs_completed, self.lr, processing_time, h, m, s)
+        if log:
+            logging.info(line_a)
+            logging.info(line_b)
+        else:
+            print(line_a)
+            print(line_b)
+
+    def print_steps_completed(self, output_to_logging=False):
+        if self.step == 0:
+            return
+        processing_time = self.total_time / self.step
+        h = self.total_time // (60 * 60)
+        m = (self.total_time - h * 60 * 60) // 60
+        s = (self.total_time - h * 60 * 60 - m * 60)
+        status = "Finished at Total Epoch:%d Steps:%s Time:%02d:%02d:%02d (%2.3fsec/step) %d x %d x %d patches" % (
+            self.epochs_completed, "{:,}".format(self.step), h, m, s, processing_time,
+            self.batch_image_size, self.batch_image_size, self.training_images)
+        if output_to_logging:
+            logging.info(status)
+        else:
+            print(status)
+
+    def copy_log_to_archive(self, archive_name):
+        """tf_graph.py:251-261 archives the TensorBoard log directory; there is none here, so the text log is archived."""
+        if not self.log_filename or not os.path.isfile(self.log_filename):
+            return
+        archive_directory = self.tf_log_dir + "_" + archive_name
+        util.make_dir(archive_directory)
+        target = os.path.join(archive_directory, self.name + "_" + os.path.basename(self.log_filename))
+        try:
+            shutil.copyfile(self.log_filename, target)
+            print("log archived to [%s]." % target)
+        except OSError as e:
+            print(e)
 
     # ---- inference (DCSCN.py:547-586) ----------------------------------------------------------
     def do(self, input_image, bicubic_input_image=None):

@@ -3,7 +3,7 @@ the absl-like registry of ``dcscn-super-resolution_amd/flags.py`` instead of ``t
 
 Usage is unchanged:  ``from helper import args``; ``args.flags.DEFINE_string(...)``;
 ``FLAGS = args.get()``; and ``args.run(main)`` where the reference calls ``tf.app.run()``.
-Training-only flags are accepted (so existing command lines keep parsing) but nothing reads them.
+The training flags drive train.py (SuperResolution.build_optimizer / train_batch on the engine's training plan).
 """
 
 import sys
@@ -38,41 +38,41 @@ _TABLE = [
     (_I, "self_ensemble", 8, "flipped / rotated copies averaged per image, 1 to 8"),
     (_B, "batch_norm", False, "batch normalisation (not implemented)"),
     (_B, "depthwise_separable", False, "depthwise-separable convs in place of every conv"),
-    # ---- training (args.py:39-59), parsed for command-line compatibility only
-    (_B, "bicubic_init", True, "training only"),
-    (_F, "clipping_norm", 5, "training only"),
+    # ---- training (args.py:39-59)
+    (_B, "bicubic_init", True, "unused (the reference defines it but never reads it)"),
+    (_F, "clipping_norm", 5, "clip the gradients by their global norm to this value; 0 = no clipping"),
     (_S, "initializer", "he", "weight initialiser used before a checkpoint is loaded"),
-    (_F, "weight_dev", 0.01, "training only"),
-    (_F, "l2_decay", 0.0001, "training only"),
-    (_S, "optimizer", "adam", "training only"),
-    (_F, "beta1", 0.9, "training only"),
-    (_F, "beta2", 0.999, "training only"),
-    (_F, "epsilon", 1e-8, "training only"),
-    (_F, "momentum", 0.9, "training only"),
-    (_I, "batch_num", 20, "training only"),
-    (_I, "batch_image_size", 48, "training only"),
-    (_I, "stride_size", 0, "training only"),
-    (_I, "training_images", 24000, "training only"),
-    (_B, "use_l1_loss", False, "training only"),
-    (_F, "initial_lr", 0.002, "training only"),
-    (_F, "lr_decay", 0.5, "training only"),
-    (_I, "lr_decay_epoch", 9, "training only"),
-    (_F, "end_lr", 2e-5, "training only"),
+    (_F, "weight_dev", 0.01, "stddev of the initialiser when --initializer is stddev"),
+    (_F, "l2_decay", 0.0001, "weight of the l2 loss of the conv filters"),
+    (_S, "optimizer", "adam", "adam, momentum or gd (adadelta, adagrad and rmsprop are not supported)"),
+    (_F, "beta1", 0.9, "beta1 of adam"),
+    (_F, "beta2", 0.999, "beta2 of adam"),
+    (_F, "epsilon", 1e-8, "epsilon of adam (TF placement: added to sqrt(v))"),
+    (_F, "momentum", 0.9, "momentum of the momentum optimizer"),
+    (_I, "batch_num", 20, "patches per training step"),
+    (_I, "batch_image_size", 48, "LR size of a training patch"),
+    (_I, "stride_size", 0, "patch stride of --build_batch (not supported)"),
+    (_I, "training_images", 24000, "patches per training epoch"),
+    (_B, "use_l1_loss", False, "train on mean |diff| instead of the mse"),
+    (_F, "initial_lr", 0.002, "initial learning rate"),
+    (_F, "lr_decay", 0.5, "learning rate factor every lr_decay_epoch epochs"),
+    (_I, "lr_decay_epoch", 9, "epochs between learning rate decays"),
+    (_F, "end_lr", 2e-5, "training stops when the learning rate falls to this"),
     # ---- datasets (args.py:62-65)
-    (_S, "dataset", "bsd200", "training only"),
+    (_S, "dataset", "bsd200", "training image directory under data_dir"),
     (_S, "test_dataset", "set5", "directory under data_dir to evaluate: set5, set14, bsd100, ... or all"),
     (_I, "tests", 1, "number of trained models (trials) to evaluate"),
-    (_B, "do_benchmark", False, "training only"),
+    (_B, "do_benchmark", False, "after training, also evaluate set5, set14 and bsd100"),
     # ---- image processing (args.py:68-74)
     (_F, "max_value", 255, "pixel value range the network works in"),
     (_I, "channels", 1, "image channels fed to the network; only 1 (Y of YCbCr) is supported"),
     (_I, "psnr_calc_border_size", -1, "border shaved before PSNR; negative means the scale factor"),
-    (_B, "build_batch", False, "training only"),
+    (_B, "build_batch", False, "pre-cut training patches (BatchDataSets): not supported"),
     # ---- environment (args.py:77-85)
     (_S, "checkpoint_dir", "models", "directory of the TF checkpoints"),
     (_S, "graph_dir", "graphs", "unused"),
     (_S, "data_dir", "data", "directory of the image datasets"),
-    (_S, "batch_dir", "batch_data", "training only"),
+    (_S, "batch_dir", "batch_data", "directory of --build_batch patches (not supported)"),
     (_S, "output_dir", "output", "directory result images are written to"),
     (_S, "tf_log_dir", "tf_log", "unused (no TensorBoard)"),
     (_S, "log_filename", "log.txt", "log file"),

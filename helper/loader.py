@@ -1,5 +1,10 @@
-"""``helper.loader`` of the reference, inference subset (loader.py:27-67).  The training datasets
-(BatchDataSets / DynamicDataSets) are out of scope."""
+"""``helper.loader`` of the reference (loader.py:27-67 and DynamicDataSets, loader.py:278-355).  BatchDataSets
+(--build_batch true, pre-cut patch files) is not supported."""
+
+import logging
+import random
+
+import numpy as np
 
 import dcscn_amd  # noqa: F401
 from dcscn_amd import imaging as util
@@ -21,3 +26,76 @@ def load_input_image(filename, width=0, height=0, channels=1, scale=1, alignment
                      print_console=True):
     image = util.load_image(filename, print_console=print_console)
     return build_input_image(image, width, height, channels, scale, alignment, convert_ycbcr)
+
+
+class DynamicDataSets:
+    """Random patches of the images of a directory (loader.py:278-355), with the reference's sequence of ``random``
+    calls: a shuffled image order (random.sample), a crop of batch_image_size * scale (randrange per axis), fliplr with
+    probability 1/2 (randrange(2)), then the LR and bicubic images by util.resize_image_by_pil.  Decoded images are
+    cached in memory."""
+
+    def __init__(self, scale, batch_image_size, channels=1, resampling_method="bicubic"):
+        self.scale = scale
+        self.batch_image_size = batch_image_size
+        self.channels = channels
+        self.resampling_method = resampling_method
+        self.filenames = []
+        self.count = 0
+        self.batch_index = None
+        self.index = 0
+        self._cache = {}
+
+    def set_data_dir(self, data_dir):
+        self.filenames = util.get_files_in_directory(data_dir)
+        self.count = len(self.filenames)
+        if self.count <= 0:
+            logging.error("Data Directory is empty.")
+            exit(-1)
+
+    def init_batch_index(self):
+        self.batch_index = random.sample(range(0, self.count), self.count)
+        self.index = 0
+
+    def get_next_image_no(self):
+        if self.index >= self.count:
+            self.init_batch_index()
+        image_no = self.batch_index[self.index]
+        self.index += 1
+        return image_no
+
+    def load_batch_image(self, max_value):
+        image = None
+        while image is None:
+            image = self.load_random_patch(self.filenames[self.get_next_image_no()])
+        if random.randrange(2) == 0:
+            image = np.fliplr(image)
+        input_image = util.resize_image_by_pil(image, 1 / self.scale, resampling_method=self.resampling_method)
+        input_bicubic_image = util.resize_image_by_pil(input_image, self.scale, resampling_method=self.resampling_method)
+        if max_value != 255:
+            scale = max_value / 255.0
+            input_image = np.multiply(input_image, scale)
+            input_bicubic_image = np.multiply(input_bicubic_image, scale)
+            image = np.multiply(image, scale)
+        return input_image, input_bicubic_image, image
+
+    def load_random_patch(self, filename):
+        image = self._cache.get(filename)
+        if image is None:
+            image = util.load_image(filename, print_console=False)
+            self._cache[filename] = image
+        height, width = image.shape[0:2]
+        load_batch_size = self.batch_image_size * self.scale
+        if height < load_batch_size or width < load_batch_size:
+            print("Error: %s should have more than %d x %d size." % (filename, load_batch_size, load_batch_size))
+            return None
+        y = 0 if height == load_batch_size else random.randrange(height - load_batch_size)
+        x = 0 if width == load_batch_size else random.randrange(width - load_batch_size)
+        image = image[y:y + load_batch_size, x:x + load_batch_size, :]
+        return build_input_image(image, channels=self.channels, convert_ycbcr=True)
+
+
+class BatchDataSets:
+    """--build_batch true (loader.py:86-275): not supported."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("--build_batch true (BatchDataSets) is not supported; use --build_batch false")

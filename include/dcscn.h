@@ -15,6 +15,9 @@
  *   self-ensemble loop of do()              (DCSCN.py:559-573)      dcscn_forward_ensemble
  *   logging "Complexity" / layer list       (DCSCN.py:331-332)      dcscn_layer_info
  *   sess.close()                                                    dcscn_destroy
+ *   build_optimizer                         (DCSCN.py:379-413)      dcscn_train_begin
+ *   sess.run(training_optimizer, ...)       (DCSCN.py:727-769)      dcscn_train_step / dcscn_train_step_device
+ *   Saver.save / restore of the slots       (tf_graph.py:251-280)   dcscn_get_tensor / dcscn_set_train_tensor
  *
  * Conventions: plain C types only; all image tensors are dense NHWC float32 with C == 1
  * (x: [n, h, w, 1], x2 / y: [n, s*h, s*w, 1], s = scale).  Weights are passed exactly as the
@@ -32,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DCSCN_ABI_VERSION 1
+#define DCSCN_ABI_VERSION 2
 #define DCSCN_MAX_NAME 128
 
 typedef struct dcscn_ctx* dcscn_handle;
@@ -305,6 +308,80 @@ int64_t dcscn_workspace_bytes(dcscn_handle h);
 /* How many workspace tensors the next forward keeps pre-split (option "p16"; 0 when the option, split16 or the graph rules it out).
  * The reference has no counterpart (sess.run hides its buffers); diagnostic for tests and benchmarks.  After dcscn_finalize. */
 int dcscn_num_presplit_tensors(dcscn_handle h);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Training (DCSCN.py:334-425, 727-769): single device, f32, non-separable pixel-shuffler nets only.
+ *
+ * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no split16, no Winograd), with
+ * dropout after the activator of every conv that has one (CNN1..L, A1, B1, B2, C, the non-final R-CNN layers; not the Up-PS
+ * convs, not the last R-CNN): out = h / keep where the mask is 1, else 0.
+ * Loss: diff = (R-CNN_last + x2) - y_true over the whole HR patch; mse = mean(diff^2); image_loss = mse, or mean(|diff|) with
+ * use_l1_loss; loss = image_loss + l2_decay * sum over every conv_W of 0.5 * ||W||^2 (biases and PReLU alphas not decayed).
+ * Gradients of `loss` for every variable; clipping (clipping_norm > 0): g <- g * c / max(||g||_global, c) over all variables;
+ * then TF's update rule:
+ *   adam:     lr_t = lr * sqrt(1 - beta2_power) / (1 - beta1_power); m <- b1 m + (1 - b1) g; v <- b2 v + (1 - b2) g^2;
+ *             w <- w - lr_t * m / (sqrt(v) + epsilon);  then beta1_power *= b1, beta2_power *= b2 (float32, start at b1, b2)
+ *   gd:       w <- w - lr g
+ *   momentum: a <- mu a + g; w <- w - lr a  (not Nesterov)
+ * Everything is deterministic: two identical sequences of calls give bit-identical variables and slots.
+ *
+ * Dropout mask (not stored; regenerated by the backward pass).  With splitmix64(z) = { z += 0x9E3779B97F4A7C15;
+ * z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31); } on uint64:
+ *   layer_key = splitmix64(dropout_key + 0x9E3779B97F4A7C15 * (layer + 1))   layer = index in dcscn_layer_info order
+ *   idx       = ((n * H + y) * W + x) * C + c                                 the element's index in the layer's NHWC output
+ *                                                                              (H, W at the layer's resolution, C = its filters)
+ *   kept     <=> (splitmix64(layer_key ^ idx) >> 40) < floor(keep_prob * 2^24)
+ * Reference values: splitmix64(0) = 0xE220A8397B1DCDAF; for dropout_key = 1, layer = 0: layer_key = 0xBEEB8DA1658EEC67 and
+ * splitmix64(layer_key ^ 0) >> 40 = 0x778B1A, splitmix64(layer_key ^ 1) >> 40 = 0x3ED40B.
+ * keep_prob = 1 turns dropout off.
+ *
+ * Variables, their gradients and the slots live on the device in flat f32 buffers, checkpoint (HWIO) layout.  Tensor names
+ * (TF's, so checkpoints interoperate): "<var>", "<var>/grad" (gradient of the total loss BEFORE clipping, of the last step
+ * or dcscn_train_gradients call), "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power".
+ * The first forward (any dcscn_forward* / evaluate / sr call) after a step re-packs the inference plan from the device
+ * variables (Training); forwards before any step are unchanged.
+ * The training workspace is separate from the inference one, sized per batch shape and bounded by "workspace_budget_bytes":
+ * a batch that does not fit returns DCSCN_ERR_NOMEM (training never tiles).
+ * --------------------------------------------------------------------------------------------------------------------- */
+typedef enum dcscn_optimizer {
+    DCSCN_OPTIMIZER_ADAM = 0,
+    DCSCN_OPTIMIZER_GD = 1,
+    DCSCN_OPTIMIZER_MOMENTUM = 2,
+    DCSCN_OPTIMIZER_ADADELTA = 3,   /* refused: DCSCN_ERR_UNSUPPORTED */
+    DCSCN_OPTIMIZER_ADAGRAD = 4,    /* refused */
+    DCSCN_OPTIMIZER_RMSPROP = 5     /* refused */
+} dcscn_optimizer;
+
+/* Training flags of helper/args.py (optimizer, beta1, beta2, epsilon, momentum, l2_decay, clipping_norm, dropout_rate,
+ * use_l1_loss). */
+typedef struct dcscn_train_config {
+    int32_t struct_size;            /* = sizeof(dcscn_train_config) */
+    int32_t optimizer;              /* dcscn_optimizer */
+    int32_t use_l1_loss;
+    int32_t reserved0;
+    double beta1, beta2, epsilon, momentum, l2_decay, clipping_norm;
+    double keep_prob;               /* --dropout_rate: probability of KEEPING a unit, (0, 1] */
+    int32_t reserved[8];
+} dcscn_train_config;
+
+/* build_optimizer: after dcscn_finalize; copies the variables to the device master copy and zeroes the slots.
+ * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable, pixel_shuffler = 0, batch_norm, adadelta / adagrad / rmsprop. */
+int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc);
+/* One training step on host buffers (x [n, h, w], x2 and y_true [n, s*h, s*w]); synchronous.  stats (optional, 4 doubles):
+ * image_loss, mse, global gradient norm before clipping, total loss (image_loss + the l2 term). */
+int dcscn_train_step(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width, double lr,
+                     uint64_t dropout_key, double* stats);
+/* The same on device buffers, enqueued on `stream` (NULL = the handle's); synchronises only when stats != NULL. */
+int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width, double lr,
+                            uint64_t dropout_key, double* stats, void* stream);
+/* Forward and backward only (gradients readable as "<var>/grad"); no update, slots untouched.  Host buffers. */
+int dcscn_train_gradients(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width,
+                          uint64_t dropout_key, double* stats);
+/* Read a variable (any time after its dcscn_set_tensor; the trained value while training), a gradient or a slot: `count`
+ * must equal its number of values. */
+int dcscn_get_tensor(dcscn_handle h, const char* name, float* out, int64_t count);
+/* Write a variable or a slot of a training handle (resume from a checkpoint). */
+int dcscn_set_train_tensor(dcscn_handle h, const char* name, const float* data, int64_t count);
 
 const char* dcscn_last_error(dcscn_handle h);
 int dcscn_destroy(dcscn_handle h);

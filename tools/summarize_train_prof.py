@@ -1,0 +1,44 @@
+"""Group the kernel statistics of a `rocprofv3 --kernel-trace --stats` run of tools/train_bench.py by training phase.
+
+    python tools/summarize_train_prof.py <rocprofv3 output dir> <steps profiled (warm-up + timed)>
+
+Phases: forward (tconv_gemm<0>, tact_fwd, td2s), dgrad (tconv_gemm<1>, tpack_dgrad), wgrad (tconv_wgrad, treduce_wgrad,
+tcol_*, tact_bwd), loss (tloss, tsumsq, tstats), optimizer (topt, tpowers).  td2s runs in both directions and is counted
+with the forward; tact_bwd (the activator and dropout backward) is counted with the weight gradient it feeds.
+"""
+import csv
+import glob
+import json
+import os
+import sys
+
+PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tpack_dgrad")), ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tact_fwd", "td2s")),
+          ("wgrad", ("tconv_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
+          ("loss", ("tloss", "tsumsq", "tstats")), ("optimizer", ("topt", "tpowers"))]
+
+
+def main():
+    root, steps = sys.argv[1], int(sys.argv[2])
+    files = glob.glob(os.path.join(root, "**", "*kernel_stats.csv"), recursive=True)
+    if not files:
+        sys.exit("no *kernel_stats.csv under %s" % root)
+    ms = {p: 0.0 for p, _ in PHASES}
+    other = 0.0
+    for f in files:
+        with open(f) as fh:
+            for row in csv.DictReader(fh):
+                name, total_ns = row["Name"], float(row["TotalDurationNs"])
+                for phase, keys in PHASES:
+                    if any(k in name for k in keys):
+                        ms[phase] += total_ns / 1e6
+                        break
+                else:
+                    other += total_ns / 1e6
+    per_step = {p: round(v / steps, 4) for p, v in ms.items()}
+    per_step["not_training"] = round(other / steps, 4)
+    per_step["kernel_sum"] = round(sum(ms.values()) / steps, 4)
+    print(json.dumps({"ms_per_step_by_phase": per_step, "steps": steps, "files": [os.path.relpath(f, root) for f in files]}))
+
+
+if __name__ == "__main__":
+    main()

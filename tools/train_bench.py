@@ -1,0 +1,167 @@
+"""Training step time of the HIP path (dcscn_train_step_device) and of a torch-ROCm fp32 autograd + Adam step of the same net.
+
+Prints one JSON line: ms per step (median over --steps after --warmup, HIP events), the conv FLOPs of one step and their rate
+as a fraction of the 157.3 TFLOP/s f32 matrix peak, and -- from a child process of its own -- the torch step time.  The split
+into forward / dgrad / wgrad / loss / optimizer comes from a separate profiler run of this script with --no-torch
+(tools/summarize_train_prof.py groups the kernel names).
+
+    python tools/train_bench.py --config L7_x2 --batch 20 --size 48
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import dcscn_oracle as O  # noqa: E402
+
+CONFIGS = {
+    "L7_x2": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
+                  reconstruct_layers=0, pixel_shuffler_filters=1),
+    "L12_x2": dict(),
+}
+PEAK_F32_MATRIX = 157.3e12
+
+
+def step_flops(cfg, n, h, w):
+    """f32 FLOPs of the convs of one step: forward, data gradient (not for CNN1) and weight gradient, 2 per MAC each."""
+    total = 0
+    first = True
+    res = 1
+    for op in O.build_topology(cfg):
+        if op["op"] == "depth_to_space":
+            res *= op["block"]
+        if op["op"] != "conv":
+            continue
+        macs = n * h * w * res * res * op["k"] * op["k"] * op["cin"] * op["cout"]
+        total += 2 * macs * (2 if first else 3)
+        first = False
+    return total
+
+
+def flags():
+    return dict(optimizer="adam", beta1=0.9, beta2=0.999, epsilon=1e-8, l2_decay=1e-4, clipping_norm=5.0, dropout_rate=0.8)
+
+
+def batch(cfg, n, h, w):
+    rng = np.random.default_rng(0)
+    s = cfg["scale"]
+    x = rng.uniform(0, 255, (n, h, w, 1)).astype(np.float32)
+    x2 = np.repeat(np.repeat(x, s, axis=1), s, axis=2)
+    y = (x2 + rng.normal(0, 8, x2.shape)).astype(np.float32)
+    return x, x2, y
+
+
+def bench_hip(cfg, n, h, w, steps, warmup):
+    from dcscn_amd import engine
+    eng = engine.Engine(cfg, device=0)
+    eng.load_weights(O.synthetic_weights(cfg, seed=0))
+    eng.train_begin(flags())
+    x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, h, w))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()          # a real stream: the events below are recorded where the steps run
+    sp = stream.cuda_stream
+    for i in range(warmup):
+        eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, h, w, 1e-4, i, stream=sp, want_stats=False)
+    torch.cuda.synchronize()
+    times = []
+    for i in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, h, w, 1e-4, warmup + i, stream=sp, want_stats=False)
+        b.record(stream)
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    eng.close()
+    return float(np.median(times)), float(np.min(times))
+
+
+def bench_torch(cfg, n, h, w, steps, warmup):
+    """The same net as torch fp32 modules on the GPU: autograd + torch.optim.Adam (dropout included)."""
+    import torch.nn.functional as F
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device("cuda")
+    params = {k: torch.tensor(v, device=dev, requires_grad=True) for k, v in O.synthetic_weights(cfg, seed=0).items()}
+    conv_w = {k: v for k, v in params.items() if k.endswith("/conv_W")}
+    opt = torch.optim.Adam(params.values(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8)
+    x, x2, y = (torch.from_numpy(a).to(dev).permute(0, 3, 1, 2).contiguous() for a in batch(cfg, n, h, w))
+    ops = O.build_topology(cfg)
+
+    def step():
+        t = {"x": x, "x2": x2}
+        for op in ops:
+            if op["op"] == "conv":
+                v = op["var"]
+                z = F.conv2d(t[op["src"]], params[v + "/conv_W"].permute(3, 2, 0, 1), padding=op["k"] // 2)
+                if op["bias"]:
+                    z = z + params[v + "/conv_B"].view(1, -1, 1, 1)
+                if op["act"] == "prelu":
+                    z = F.dropout(torch.where(z > 0, z, params[v + "/prelu/" + op["name"] + "_prelu"].view(1, -1, 1, 1) * z), 0.2)
+                elif op["act"]:
+                    z = F.dropout(F.relu(z), 0.2)
+                t[op["dst"]] = z
+            elif op["op"] == "concat":
+                t[op["dst"]] = torch.cat([t[s] for s in op["srcs"]], 1)
+            elif op["op"] == "depth_to_space":
+                t[op["dst"]] = F.pixel_shuffle(t[op["src"]], op["block"])
+            elif op["op"] == "add":
+                t[op["dst"]] = t[op["srcs"][0]] + t[op["srcs"][1]]
+        loss = F.mse_loss(t["y_"], y) + 1e-4 * sum(0.5 * (wt * wt).sum() for wt in conv_w.values())
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(list(params.values()), 5.0)
+        opt.step()
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="L7_x2", choices=sorted(CONFIGS))
+    ap.add_argument("--batch", type=int, default=20)
+    ap.add_argument("--size", type=int, default=48)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison (profiler runs)")
+    ap.add_argument("--torch-only", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    cfg = O.make_config(**CONFIGS[a.config])
+    if a.torch_only:
+        print(json.dumps({"torch_ms_per_step": bench_torch(cfg, a.batch, a.size, a.size, a.steps, a.warmup)}))
+        return
+    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup)
+    flops = step_flops(cfg, a.batch, a.size, a.size)
+    out = dict(config=a.config, batch=a.batch, lr_size=a.size, steps=a.steps, warmup=a.warmup, ms_per_step=round(med, 4),
+               ms_per_step_min=round(best, 4), conv_gflop_per_step=round(flops / 1e9, 3),
+               conv_tflops=round(flops / (med * 1e-3) / 1e12, 3), fraction_of_f32_matrix_peak=round(flops / (med * 1e-3) / PEAK_F32_MATRIX, 4))
+    if not a.no_torch:
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", a.config, "--batch", str(a.batch), "--size", str(a.size),
+                            "--steps", str(a.steps), "--warmup", str(a.warmup), "--torch-only"], capture_output=True, text=True, timeout=900)
+        if p.returncode == 0:
+            out.update(json.loads(p.stdout.strip().splitlines()[-1]))
+        else:
+            out["torch_error"] = (p.stderr or p.stdout).strip().splitlines()[-1:]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
