@@ -365,6 +365,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->conv3_h8 = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "nin_h8")) {                   // any time: both workgroup sizes take the same filter image
+        h->nin_h8 = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "debug_digest")) {            // debug aid: a checksum of the whole workspace behind every launch (dcscn_debug_digests)
         if ((int)h->ops.size() + 1 > 1024) return fail(h, DCSCN_ERR_UNSUPPORTED, "debug_digest: more than 1023 launches");
         h->debug_digest = value != 0;
@@ -431,9 +435,6 @@ static int forward_host_chunked(dcscn_ctx* h, const float* x, const float* x2, f
         HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         h->host_ev.push_back(e);
     }
-    const bool trace = getenv("DCSCN_TRACE_HOST") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
     int begin[5];
     for (int i = 0; i <= chunks; ++i) begin[i] = (int)((int64_t)n * i / chunks);
     // the first chunk must be the largest: it sizes the workspace carve the later ones reuse
@@ -459,7 +460,6 @@ static int forward_host_chunked(dcscn_ctx* h, const float* x, const float* x2, f
         if (i > 0 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(chunks - 1))) return rc;
-    if (trace) fprintf(stderr, "dcscn_forward: %d chunk(s), %.2f ms\n", chunks, now() - t0);
     return DCSCN_OK;
 }
 

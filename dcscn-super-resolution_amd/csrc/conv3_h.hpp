@@ -37,9 +37,6 @@
 #include "conv_wino2.hpp"
 #include "split16.hpp"
 #include "p16.hpp"
-#ifndef C3H_EXP
-#define C3H_EXP 0
-#endif
 
 namespace dcscn {
 
@@ -106,16 +103,11 @@ constexpr bool c3h_writes_conflict_free() {
 static_assert(c3h_reads_conflict_free(), "c3h_unit: a ds_read_b128 lane group must see 16 distinct (column parity, unit) pairs");
 static_assert(c3h_writes_conflict_free(), "c3h_unit: the two columns of an image store must fill a record's banks exactly once");
 
-// ABL (tuner only, tools/h16_tune.hip; results are wrong by design): 0 shipped; 1 no convert + write of the input image after the
-// first chunk; 2 nor its global loads; 3 no filter staging after the first tap; 4 no per-tap barrier; 5 one MFMA product of three;
-// 6 = 2 + 3 + 4 (LDS reads and MFMAs only); 7 / 8 = shipped + shader-clock probes (per wave, through a.srctab: [0] entry, [1] K loop
-// start, [2] K loop end, [3] exit, [4] sum over taps of (wait + barrier) [7] or of the DMA / load issue behind it [8], [5] sum of the
-// chunk-boundary barrier + image write, [6] HW_ID)
 // IN16: the input is a P16 tensor (a.in16, p16.hpp): the staged item is one 16-byte (hi | lo) unit -- fetched with the c3h_unit
 // permutation on the source side, written to LDS as it is (ds_write_b128 at the lane-linear position), out-of-image pixels and octets past
 // the tensor's last read the plane's zero record: no conversion, no select, half the LDS store instructions.
 // Destinations may be P16 tensors (OutDesc::p16), each on its own: the epilogue then stores (hi | lo) units.
-template <int NT, int NTV, int ABL = 0, bool IN16 = false>
+template <int NT, int NTV, bool IN16 = false>
 __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int tile_id, int ntile) {
     using G = C3HGeom<NT>;
     const int tid = threadIdx.x;
@@ -123,9 +115,6 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lj = lane & 15;
     const int lk = lane >> 4;
-    constexpr bool PROBE = ABL == 7 || ABL == 8;
-    long long pr_t0 = 0, pr_t1 = 0, pr_t2 = 0, pr_sum = 0, pr_cb = 0, pr_a = 0;
-    if constexpr (PROBE) pr_t0 = __builtin_readcyclecounter();
 
     int bid = tile_id;
     const int tx = bid % a.tiles_x;
@@ -282,7 +271,6 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
     // tap): no value in the loop depends on a branch, so the compiler keeps ONE register set for the staged values.
     const int octs = a.tail_octs;                              // 0, or 1 / 2 / 3: the last chunk is a packed tail (below)
     const int n_main = octs ? n_chunks - 1 : n_chunks;
-    if constexpr (PROBE) pr_t1 = __builtin_readcyclecounter();
     for (int chunk = 0; chunk < n_main; ++chunk) {
         const bool more = chunk + 1 < n_chunks;                // block uniform
         const int nchunk = more ? chunk + 1 : chunk;
@@ -297,15 +285,11 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
             constexpr int slot = step % 3;                     // (chunk * 9 + step) % 3
             constexpr int step2 = (step + 2) % 9;              // the step two ahead: packed tap (ky2 * 3 + kx2) of this or the next chunk
             constexpr int ptap2 = (step2 % 3) * 3 + step2 / 3;
-            if constexpr (ABL == 7) pr_a = __builtin_readcyclecounter();
-            if constexpr (ABL != 3 && ABL != 6) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::F_ROUNDS) : "memory");
-            if constexpr ((ABL != 4 && ABL != 6) || step == 0) __syncthreads();
-            if constexpr (ABL == 7) pr_sum += __builtin_readcyclecounter() - pr_a;
-            if constexpr (ABL == 8) pr_a = __builtin_readcyclecounter();
-            if constexpr (ABL != 3 && ABL != 6)             // past the end: a re-fetch nobody reads; the tail's slots are in step order
-                dma_f(step + 2 < 9 ? chunk * 9 + ptap2 : nchunk * 9 + (to_tail ? step2 : ptap2), (step + 2) % 3);
-            if constexpr (step == 0 && ABL != 2 && ABL != 6) load_in(nchunk);
-            if constexpr (ABL == 8) pr_sum += __builtin_readcyclecounter() - pr_a;
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::F_ROUNDS) : "memory");
+            __syncthreads();
+            // past the end: a re-fetch nobody reads; the tail's slots are in step order
+            dma_f(step + 2 < 9 ? chunk * 9 + ptap2 : nchunk * 9 + (to_tail ? step2 : ptap2), (step + 2) % 3);
+            if constexpr (step == 0) load_in(nchunk);
             if constexpr (ky == 0) b_hi = b_col(std::integral_constant<int, kx>{});
             static_for<(ky == 0 ? 0 : 3), 4>([&](auto m_) DCSCN_INL {
                 constexpr int row = ky + decltype(m_)::value;
@@ -313,7 +297,6 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
                 xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
             });
             const char* fs = smem + a_lane + slot * G::F_TAP_BYTES;
-#if C3H_EXP == 0
             static_for<0, NTV>([&](auto n_) DCSCN_INL {
                 constexpr int n = decltype(n_)::value;
                 const h8 wh = *reinterpret_cast<const h8*>(fs + (2 * n) * 1024);
@@ -321,51 +304,18 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
                 static_for<0, 4>([&](auto m_) DCSCN_INL {
                     constexpr int m = decltype(m_)::value;
                     constexpr int q = (ky + m) & 3;
-                    if constexpr (ABL != 5) {
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
-                    }
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[q], acc[m][n], 0, 0, 0);
                 });
             });
-#else
-            // experiment (tools/h16_tune, -DC3H_EXP=1/3): products outermost per tile (an accumulator is touched every 4th MFMA);
-            // bit 1: the A fragments of tile n + 1 are read into a second register pair before tile n's MFMAs, order pinned
-            {
-                h8 whb[2], wlb[2];
-                whb[0] = *reinterpret_cast<const h8*>(fs);
-                wlb[0] = *reinterpret_cast<const h8*>(fs + 1024);
-                static_for<0, NTV>([&](auto n_) DCSCN_INL {
-                    constexpr int n = decltype(n_)::value;
-                    constexpr int cb = (C3H_EXP & 2) ? (n & 1) : 0;
-                    if constexpr ((C3H_EXP & 2) != 0) {
-                        if constexpr (n + 1 < NTV) {
-                            whb[(n + 1) & 1] = *reinterpret_cast<const h8*>(fs + (2 * n + 2) * 1024);
-                            wlb[(n + 1) & 1] = *reinterpret_cast<const h8*>(fs + (2 * n + 3) * 1024);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        }
-                    } else if constexpr (n > 0) {
-                        whb[0] = *reinterpret_cast<const h8*>(fs + (2 * n) * 1024);
-                        wlb[0] = *reinterpret_cast<const h8*>(fs + (2 * n + 1) * 1024);
-                    }
-                    static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlb[cb], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
-                    static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[cb], xl[(ky + m) & 3], acc[m][n], 0, 0, 0); });
-                    static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(whb[cb], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
-                    if constexpr ((C3H_EXP & 2) != 0) __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-                });
-            }
-#endif
             // the next chunk's input values become (hi, lo) pairs two items per tap from step 3 on
-            if constexpr (step >= 3 && ABL != 1 && ABL != 2 && ABL != 6)
+            if constexpr (step >= 3)
                 static_for<2 * (step - 3), (2 * (step - 3) + 2 < G::IN_ROUNDS ? 2 * (step - 3) + 2 : G::IN_ROUNDS)>([&](auto r_) DCSCN_INL { convert_in(r_, nchunk); });
         });
-        if constexpr (ABL != 1 && ABL != 2 && ABL != 6) {
-            if (more) {
-                if constexpr (PROBE) pr_a = __builtin_readcyclecounter();
-                __syncthreads();                              // every wave is past its last read of this chunk's image
-                store_in();                                   // made visible by the barrier in front of the next tap
-                if constexpr (PROBE) pr_cb += __builtin_readcyclecounter() - pr_a;
-            }
+        if (more) {
+            __syncthreads();                                  // every wave is past its last read of this chunk's image
+            store_in();                                       // made visible by the barrier in front of the next tap
         }
     }
     // Packed tail (kernels.h: c3h_tail_octs): the last chunk holds at most 8 / 16 / 24 channels = 1 / 2 / 3 octets, so its
@@ -410,7 +360,6 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the clamped re-fetches of the last two taps
-    if constexpr (PROBE) pr_t2 = __builtin_readcyclecounter();
 
     // ---- epilogue ----
     const int cbase = ntile * NT * 16 + 4 * lk;                                  // bias / slope index: padded group layout
@@ -624,22 +573,11 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
     else if (act == ACT_NONE) finish(std::integral_constant<int, ACT_NONE>{});
     else finish(std::integral_constant<int, -1>{});
     if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + img] = 1; }     // the image goes to the float32 plan (exec.hip)
-    if constexpr (PROBE) {
-        if (lane == 0 && a.srctab) {
-            long long* pr = reinterpret_cast<long long*>(const_cast<void*>(a.srctab)) + ((size_t)blockIdx.x * 4 + wave) * 8;
-            unsigned hw;
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            pr[7] = xcc;
-            pr[0] = pr_t0; pr[1] = pr_t1; pr[2] = pr_t2; pr[3] = __builtin_readcyclecounter(); pr[4] = pr_sum; pr[5] = pr_cb; pr[6] = hw;
-        }
-    }
 }
 
 // 1-D grid decoded as conv_wino2's: the channel groups of one pixel tile get ids that are congruent mod 8 and close together
 // (same XCD, about the same time: the input tile is shared through that XCD's L2)
-template <int NT, int WPS = 2, int ABL = 0, bool IN16 = false>
+template <int NT, int WPS = 2, bool IN16 = false>
 __global__ __launch_bounds__(256, WPS) void conv3_h(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_c3h[];
     const int Gn = a.n_groups, S = a.group_span;
@@ -654,8 +592,8 @@ __global__ __launch_bounds__(256, WPS) void conv3_h(const ConvArgs a) {
     const int ntile = phase * S + (r >> 3);
     const int tile_id = q * 8 + (r & 7);
     if (tile_id >= a.N * a.tiles_y * a.tiles_x) return;
-    if (ntile < a.n_full) conv3_h_body<NT, NT, ABL, IN16>(a, smem_c3h, tile_id, ntile);                 // block uniform
-    else if constexpr (NT >= 2) conv3_h_body<NT, NT - 1, ABL, IN16>(a, smem_c3h, tile_id, ntile);
+    if (ntile < a.n_full) conv3_h_body<NT, NT, IN16>(a, smem_c3h, tile_id, ntile);                 // block uniform
+    else if constexpr (NT >= 2) conv3_h_body<NT, NT - 1, IN16>(a, smem_c3h, tile_id, ntile);
 }
 
 }  // namespace dcscn

@@ -17,10 +17,10 @@
 //   half 1:  | COMPUTE(t-1) LOAD(t)    | COMPUTE(t)   LOAD(t+1)    | ...                   ( | = s_barrier )
 //
 // so that a SIMD's matrix pipe goes from one wave to the other inside a segment without anybody waiting at a barrier for it (the
-// first r04 build separated the parts by a second barrier -- C3E_SB = 0, kept for the tuner: a segment then lasted as long as its
-// slowest wave, twice per tap).  Half 1 runs at s_setprio 1: its MFMAs and, behind them, its load part win the issue arbitration
-// against the partner wave of the SIMD (-4 % on the two-group layers; raising the priority per phase instead, or for half 0, gains
-// nothing: profiles/r04_h16_conv3_harness.txt).
+// first r04 build separated the parts by a second barrier: a segment then lasted as long as its slowest wave, twice per tap).
+// Half 1 runs at s_setprio 1: its MFMAs and, behind them, its load part win the issue arbitration against the partner wave of the
+// SIMD (-4 % on the two-group layers; raising the priority per phase instead, or for half 0, gains nothing:
+// profiles/r04_h16_conv3_harness.txt).
 //
 // * input image: ONE (hi, lo) image per 32-channel chunk for both halves, double buffered (2 x 41.5 KB): the 2592 (pixel, channel quad)
 //   items of chunk c + 1 are loaded at step 0 of chunk c by all 512 threads (6 loads each, hand-written so that the compiler's wait
@@ -58,7 +58,7 @@ __device__ __forceinline__ void c3p_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 // conv_wino2.hpp's glds16 with M0 declared clobbered instead of saved and restored around every piece (two s_mov fewer per DMA)
 __device__ __forceinline__ void glds16c(const void* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" DCSCN_GLDS_AUX : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
 }
 
 template <int NT>
@@ -77,23 +77,6 @@ struct C3EGeom {
     static constexpr int LDS_BYTES = BA_BASE + 4 * NT * 128;
 };
 
-// DBG (tuner only) 1: per wave through a.srctab: [0] entry, [1] exit, [2] items, [3] sum of load phases, [4] sum of compute phases,
-// [5] sum of the waits at the barrier ending a load phase, [6] same for compute phases, [7] sum of epilogues
-#ifndef C3E_SB
-#define C3E_SB 1           // 1: one workgroup barrier per tap (see the header); 0: the two-barrier ping-pong of the first r04 build
-#endif
-#ifndef C3E_ABL
-#define C3E_ABL 0          // tuner only (results wrong): 1 no filter DMA, 2 no image staging, 4 no A-fragment reads, 8 no MFMAs, 16 no B-row reads
-#endif
-#ifndef C3E_PRIO
-#define C3E_PRIO 2         // waves of half (C3E_PRIO - 1) run at s_setprio 1 for the whole kernel; 0 = nobody
-#endif
-#ifndef C3E_PRIO_LEVEL
-#define C3E_PRIO_LEVEL 1
-#endif
-#ifndef C3E_PFD
-#define C3E_PFD 2          // A fragments are read this many channel tiles ahead of their MFMAs (the first PFD tiles in the load phase)
-#endif
 // NT = channel tiles of half 0, C1 = of half 1 (NT or NT - 1; 0 for a one-tile layer): launch constants -- the host instantiates the
 // pair a layer needs, every loop over tiles is straight-line code (a branch around a tile makes the compiler wait for ALL outstanding
 // LDS reads in front of every tile, and merging code variants cost 60 VGPRs in copies of the accumulators).
@@ -101,11 +84,11 @@ struct C3EGeom {
 // immediate offset), 0 = args.nt_pack (tuner: one group split between the halves)
 // P16 = the input is a pre-split tensor (a.in16, p16.hpp) staged by LDS-DMA, and the destinations are P16 tensors too (the layers this
 // kernel runs feed split16 consumers only); false = float32 NHWC in and out, split in registers (r04)
-template <int NT, int C1, int DBG = 0, int NTP = NT, bool P16 = false>
+template <int NT, int C1, int NTP = NT, bool P16 = false>
 __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     static_assert(C1 == NT || C1 == NT - 1, "half 1 takes as many tiles as half 0 or one fewer");
-    static_assert(!P16 || C3E_SB, "P16 staging is written for the one-barrier schedule");
-    constexpr int PFD = C3E_PFD < NT ? C3E_PFD : (NT > 1 ? NT - 1 : 1), NB = PFD + 1;
+    // A fragments are read PFD channel tiles ahead of their MFMAs (the first PFD tiles in the load phase)
+    constexpr int PFD = 2 < NT ? 2 : (NT > 1 ? NT - 1 : 1), NB = PFD + 1;
     using G = C3EGeom<NT>;
     extern __shared__ __attribute__((aligned(16))) char smem_c3e[];
     char* const smem = smem_c3e;
@@ -129,9 +112,6 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     const unsigned f_off = (unsigned)(lane * 16);
     const int cq = tid & 7;
     const int tap_stride = ntp * 2048;                         // bytes between taps of a group's filter image
-    long long pr_t0 = 0, pr_load = 0, pr_comp = 0, pr_bl = 0, pr_bc = 0, pr_epi = 0, pr_a = 0, pr_b = 0;
-    int pr_items = 0;
-    if constexpr (DBG == 1) pr_t0 = __builtin_readcyclecounter();
 
     // ---- what this half does of an item: channel group g, its tiles [o, o + cnt) ----
     struct Unit {
@@ -245,13 +225,11 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
         const bool ok = ((mask >> r) & 1u) && kq < rem;
         const unsigned voff = ok ? 128u + (unsigned)(pix0 + hrow * W + hcol) * (unsigned)rec + (unsigned)((2 * kq + part) * 16) : (unsigned)(s * 16);
         const int piece = r < L - 1 ? wave + 8 * r : 40;
-        if constexpr (C3E_ABL & 2) return;
         glds16c(base, voff, lds0 + (unsigned)(buf * G::IN_BUF + piece * 1024));
     };
     // one tap of this half's filters -> ring slot
     auto dma_f = [&](const char* src, int slot /* byte offset of the ring slot */, int cnt) DCSCN_INL {
         const int pieces = cnt > 0 ? 2 * cnt : 1;
-        if constexpr (C3E_ABL & 1) return;
         static_for<0, F>([&](auto r_) DCSCN_INL {
             constexpr int r = decltype(r_)::value;
             const int piece = (w4 + 4 * r) % pieces;
@@ -272,8 +250,8 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     constexpr int CNT = decltype(cnt_c)::value;                // channel tiles of THIS half
     constexpr int HALF = decltype(half_c)::value;
     // one barrier per tap: half 0 keeps the one behind its compute phase, half 1 the one behind its load phase
-    constexpr bool BAR_L = !C3E_SB || HALF == 1, BAR_C = !C3E_SB || HALF == 0;
-    constexpr bool DMA_LATE = C3E_SB && HALF == 1;             // half 1 issues a tap's DMA behind the barrier (its target slot is read until then)
+    constexpr bool BAR_L = HALF == 1, BAR_C = HALF == 0;
+    constexpr bool DMA_LATE = HALF == 1;             // half 1 issues a tap's DMA behind the barrier (its target slot is read until then)
     // ---- first item ----
     Unit cur, nxt;
     int id = blockIdx.x;
@@ -295,17 +273,10 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
         static_for<0, L>([&](auto r_) DCSCN_INL { convert_store(r_, cur.all_in, cur.ok_mask, 0, 0); });
     }
     c3p_barrier();
-    if (!C3E_SB && half == 1) c3p_barrier();                   // half 1 runs one phase behind half 0
-    if (C3E_PRIO && half == C3E_PRIO - 1) asm volatile("s_setprio %0" :: "n"(C3E_PRIO_LEVEL));
+    if (half == 1) asm volatile("s_setprio 1");                // half 1 runs at priority 1 for the whole kernel (see the header)
 
     f32x4 acc[4][NT];
     h8 xh[4], xl[4], wa[NB], wb[NB];                           // B rows (hi, lo), A fragments (wl, wh) in a ring of PFD + 1 tiles
-    if constexpr (C3E_ABL != 0) {                              // finite operands for the ablation builds (non-finite ones slow the MFMAs down)
-        u32x4 z = {0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};
-        asm volatile("" : "+v"(z));
-        static_for<0, 4>([&](auto m_) DCSCN_INL { xh[decltype(m_)::value] = xl[decltype(m_)::value] = __builtin_bit_cast(h8, z); });
-        static_for<0, NB>([&](auto m_) DCSCN_INL { wa[decltype(m_)::value] = wb[decltype(m_)::value] = __builtin_bit_cast(h8, z); });
-    }
     bool pending = false;                                      // an epilogue is owed (previous item)
     int parity = 0;
     // epilogue state of the previous item (its accumulators are still in acc until the first compute phase of the next item)
@@ -313,7 +284,6 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     bool e_full = false;
 
     auto epilogue = [&]() DCSCN_INL {
-        if constexpr (DBG == 1) pr_a = __builtin_readcyclecounter();
         const int ba = G::BA_BASE + ((parity ^ 1) * 2 + half) * NT * 128;
         const int cb16 = e_g * ntp * 16 - 16 * (e_g > a.n_full ? e_g - a.n_full : 0) + e_o * 16;   // conv channel of the half's first tile
         const float inv = a.inv_scale;
@@ -375,7 +345,6 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
             }
             if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + e_img] = 1; }     // the image goes to the float32 plan (exec.hip)
             pending = false;
-            if constexpr (DBG == 1) { pr_epi += __builtin_readcyclecounter() - pr_a; ++pr_items; }
             return;
         }
         if (fastable && e_full) {
@@ -456,16 +425,13 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
         }
         if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + e_img] = 1; }     // the image goes to the float32 plan (exec.hip)
         pending = false;
-        if constexpr (DBG == 1) { pr_epi += __builtin_readcyclecounter() - pr_a; ++pr_items; }
     };
-    auto phase_barrier = [&](auto on_c, long long& acc_wait) DCSCN_INL {
-        if constexpr (DBG == 1) pr_b = __builtin_readcyclecounter();
+    auto phase_barrier = [&](auto on_c) DCSCN_INL {
         __builtin_amdgcn_sched_barrier(0);                     // MFMAs have no memory effect: without this the scheduler moves some across the barrier
         if constexpr (decltype(on_c)::value) {
             c3p_barrier();
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (DBG == 1) acc_wait += __builtin_readcyclecounter() - pr_b;
     };
     constexpr std::integral_constant<bool, BAR_L> bar_l{};
     constexpr std::integral_constant<bool, BAR_C> bar_c{};
@@ -498,7 +464,6 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                 constexpr int step = decltype(s_)::value;
                 constexpr int kx = step / 3, ky = step % 3;
                 // ================= LOAD phase of this tap =================
-                if constexpr (DBG == 1) pr_a = __builtin_readcyclecounter();
                 // first fragments of this tap, read FIRST (their latency runs under the rest of the phase): the new B row(s) and the
                 // A fragments of the first PFD tiles -- the tap's filter slot has been complete since the previous load phase's wait
                 if constexpr (ky == 0) {
@@ -507,20 +472,17 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                     const int hx = (l & 15) + kx;
                     b_hi = img_off + (4 * w4 * G::HT + hx) * G::PIX_BYTES + c3h_unit(hx, l >> 4, 0) * 16;
                 }
-                if constexpr (!(C3E_ABL & 16))
                 static_for<(ky == 0 ? 0 : 3), 4>([&](auto m_) DCSCN_INL {
                     constexpr int row = ky + decltype(m_)::value;
                     xh[row & 3] = *reinterpret_cast<const h8*>(smem + b_hi + row * G::ROW_BYTES);
                     xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
                 });
                 const char* fs = smem + (step % 3 == 0 ? sl0 : step % 3 == 1 ? sl1 : sl2) + a_lane;
-                if constexpr (!(C3E_ABL & 4))
                 static_for<0, PFD>([&](auto p_) DCSCN_INL {
                     constexpr int p = decltype(p_)::value;
                     wb[p] = *reinterpret_cast<const h8*>(fs + (2 * p) * 1024);       // (tiles past the half's last: stale bytes of its own slot, never used)
                     wa[p] = *reinterpret_cast<const h8*>(fs + (2 * p + 1) * 1024);
                 });
-                if constexpr (!C3E_SB) { if constexpr (step == 1) c3p_wait_vm<L>(); else c3p_wait_vm<0>(); }   // the pieces issued in the previous load phase
                 auto dma_ahead = [&]() DCSCN_INL {   // the tap two steps ahead: of this chunk, of the next one, of the packed tail, or of the next item
                     constexpr int step2 = (step + 2) % 9;
                     constexpr int ptap2 = (step2 % 3) * 3 + step2 / 3;
@@ -537,16 +499,14 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                 constexpr int IMG = P16 && step >= 1 && step <= L ? 1 : 0, IMG_PREV = P16 && step >= 2 && step <= L + 1 ? 1 : 0;
                 if constexpr (P16) { if constexpr (IMG) img_piece(std::integral_constant<int, step - 1>{}, li_pix0, li_ok, lchunk, ibuf ^ 1); }
                 else {
-                    if constexpr (step == 0 && !(C3E_ABL & 2)) load_in(li_base, li_ok, lchunk);
-                    if constexpr (step >= 3 && !(C3E_ABL & 2)) convert_store(std::integral_constant<int, step - 3>{}, li_all_in, li_ok, lchunk, ibuf ^ 1);
+                    if constexpr (step == 0) load_in(li_base, li_ok, lchunk);
+                    if constexpr (step >= 3) convert_store(std::integral_constant<int, step - 3>{}, li_all_in, li_ok, lchunk, ibuf ^ 1);
                 }
                 if constexpr (step == 0) { if (chunk == 0 && pending) epilogue(); }
                 // half 1, one barrier per tap: the next tap's pieces were issued behind the previous barrier; only this step's image loads / piece are younger
                 if constexpr (DMA_LATE) { if constexpr (P16) c3p_wait_vm<IMG>(); else if constexpr (step == 0) c3p_wait_vm<L>(); else c3p_wait_vm<0>(); }
-                if constexpr (DBG == 1) pr_load += __builtin_readcyclecounter() - pr_a;
-                phase_barrier(bar_l, pr_bl);
+                phase_barrier(bar_l);
                 // ================= COMPUTE phase =================
-                if constexpr (DBG == 1) pr_a = __builtin_readcyclecounter();
                 if constexpr (DMA_LATE) { dma_ahead(); __builtin_amdgcn_sched_barrier(0); }
                 if constexpr (step == 0) {
                     if (chunk == 0)
@@ -558,19 +518,13 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                     constexpr int CNT = decltype(cnt_c)::value;
                     static_for<0, CNT>([&](auto n_) DCSCN_INL {
                         constexpr int n = decltype(n_)::value;
-                        if constexpr (n + PFD < CNT && !(C3E_ABL & 4)) {
+                        if constexpr (n + PFD < CNT) {
                             wb[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD)) * 1024);
                             wa[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD) + 1) * 1024);
                         }
-                        if constexpr (C3E_ABL & 8) {
-                            asm volatile("" :: "v"(wa[n % NB]), "v"(wb[n % NB]));
-                            asm volatile("" :: "v"(xh[0]), "v"(xl[0]), "v"(xh[1]), "v"(xl[1]));
-                            asm volatile("" :: "v"(xh[2]), "v"(xl[2]), "v"(xh[3]), "v"(xl[3]));
-                        } else {
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[n % NB], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xl[(ky + m) & 3], acc[m][n], 0, 0, 0); });
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
-                        }
                         __builtin_amdgcn_sched_barrier(0);     // a tile's reads and MFMAs stay where they are (hoisted, the reads of all tiles cost 40 more registers)
                     });
                 };
@@ -578,9 +532,8 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                 // half 0, one barrier per tap: the NEXT tap's pieces (issued in the previous load phase) must have landed before the barrier;
                 // younger than them: this load phase's F pieces, and the six image loads of a step 0 during the two steps after it
                 // P16: younger than LOAD(t - 1)'s filter pieces are its image piece (issued behind them), LOAD(t)'s F pieces and its image piece
-                if constexpr (C3E_SB && HALF == 0) { if constexpr (P16) c3p_wait_vm<F + IMG + IMG_PREV>(); else if constexpr (step <= 1) c3p_wait_vm<F + L>(); else c3p_wait_vm<F>(); }
-                if constexpr (DBG == 1) pr_comp += __builtin_readcyclecounter() - pr_a;
-                phase_barrier(bar_c, pr_bc);
+                if constexpr (HALF == 0) { if constexpr (P16) c3p_wait_vm<F + IMG + IMG_PREV>(); else if constexpr (step <= 1) c3p_wait_vm<F + L>(); else c3p_wait_vm<F>(); }
+                phase_barrier(bar_c);
                 ++tt;
             });
             ibuf ^= 1;
@@ -592,11 +545,9 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
             asm volatile("" : "+v"(l));
             auto tail_step = [&](int step, auto first_c) DCSCN_INL {
                 constexpr bool FIRST = decltype(first_c)::value;
-                if constexpr (DBG == 1) pr_a = __builtin_readcyclecounter();
-                if constexpr (!C3E_SB) { if (!FIRST && step == 1) c3p_wait_vm<L>(); else c3p_wait_vm<0>(); }
                 if constexpr (!P16)
-                if (!FIRST && step == 2 && !(C3E_ABL & 2)) {
-                    if constexpr (C3E_SB && HALF == 0) c3p_wait_vm<F>();      // the image loads of tail step 0 (younger: step 1's pieces)
+                if (!FIRST && step == 2) {
+                    if constexpr (HALF == 0) c3p_wait_vm<F>();      // the image loads of tail step 0 (younger: step 1's pieces)
                     static_for<0, L>([&](auto r_) DCSCN_INL { convert_store(r_, nxt.all_in, nxt.ok_mask, 0, ibuf ^ 1); });
                 }
                 if constexpr (!DMA_LATE) dma_f(tap_src(cur, nxt, tt + 2), sl2, CNT);
@@ -604,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                     // the next item's first image: all L pieces at tail step 1 (buffer ibuf ^ 1 is read until the barrier that ends tail step 0),
                     // behind the filter pieces; complete at the end of tail step 2 (n_tail >= 3)
                     if constexpr (!FIRST) { if (step == 1) static_for<0, L>([&](auto r_) DCSCN_INL { img_piece(r_, nxt.pix0, nxt.ok_mask, 0, ibuf ^ 1); }); }
-                } else if constexpr (FIRST && !(C3E_ABL & 2)) load_in(nxt.a_base, nxt.ok_mask, 0);
+                } else if constexpr (FIRST) load_in(nxt.a_base, nxt.ok_mask, 0);
                 const int pair = 4 * step + (l >> 4);
                 int tap = octs == 1 ? pair : octs == 2 ? pair >> 1 : (pair * 11) >> 5;
                 const int oct = pair - tap * octs;
@@ -627,9 +578,7 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                     if constexpr (P16) { if (!FIRST && step == 1) c3p_wait_vm<L>(); else c3p_wait_vm<0>(); }
                     else if constexpr (FIRST) c3p_wait_vm<L>(); else c3p_wait_vm<0>();
                 }
-                if constexpr (DBG == 1) pr_load += __builtin_readcyclecounter() - pr_a;
-                phase_barrier(bar_l, pr_bl);
-                if constexpr (DBG == 1) pr_a = __builtin_readcyclecounter();
+                phase_barrier(bar_l);
                 if constexpr (DMA_LATE) { dma_f(tap_src(cur, nxt, tt + 2), sl2, CNT); __builtin_amdgcn_sched_barrier(0); }
                 auto mfmas = [&](auto cnt_c) DCSCN_INL {
                     constexpr int CNT = decltype(cnt_c)::value;
@@ -646,12 +595,11 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                     });
                 };
                 mfmas(std::integral_constant<int, CNT>{});
-                if constexpr (C3E_SB && HALF == 0) {
+                if constexpr (HALF == 0) {
                     if constexpr (P16) { if (!FIRST && step == 1) c3p_wait_vm<F + L>(); else c3p_wait_vm<F>(); }
                     else if (FIRST || step == 1) c3p_wait_vm<F + L>(); else c3p_wait_vm<F>();
                 }
-                if constexpr (DBG == 1) pr_comp += __builtin_readcyclecounter() - pr_a;
-                phase_barrier(bar_c, pr_bc);
+                phase_barrier(bar_c);
                 ++tt;
                 { const int t = sl0; sl0 = sl1; sl1 = sl2; sl2 = t; }   // the ring moves on by one slot per tail step
             };
@@ -669,17 +617,10 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
         decode(id + (int)gridDim.x, nxt);
     }
     epilogue();
-    if (!C3E_SB && half == 0) c3p_barrier();                   // pairs with half 1's extra barrier at the start
     };
     if (half == 0) run(std::integral_constant<int, NT>{}, std::integral_constant<int, 0>{});
     else run(std::integral_constant<int, C1>{}, std::integral_constant<int, 1>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // no LDS-DMA may land after the workgroup has given its LDS back
-    if constexpr (DBG == 1) {
-        if (lane == 0 && a.srctab) {
-            long long* pr = reinterpret_cast<long long*>(const_cast<void*>(a.srctab)) + ((size_t)blockIdx.x * 8 + wave) * 8;
-            pr[0] = pr_t0; pr[1] = __builtin_readcyclecounter(); pr[2] = pr_items; pr[3] = pr_load; pr[4] = pr_comp; pr[5] = pr_bl; pr[6] = pr_bc; pr[7] = pr_epi;
-        }
-    }
 }
 
 }  // namespace dcscn

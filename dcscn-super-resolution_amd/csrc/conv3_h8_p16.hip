@@ -5,7 +5,7 @@ namespace dcscn {
 
 template <int NT, int C1>
 static hipError_t c3e16_set_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_h8<NT, C1, 0, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<NT>::LDS_BYTES);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_h8<NT, C1, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<NT>::LDS_BYTES);
 }
 
 hipError_t c3e16_init_kernels() {
@@ -19,7 +19,7 @@ hipError_t c3e16_init_kernels() {
 
 template <int NT, int C1>
 static hipError_t c3e16_launch_one(const ConvArgs& a, int wgs, hipStream_t stream) {
-    hipLaunchKernelGGL((conv3_h8<NT, C1, 0, NT, true>), dim3((unsigned)wgs), dim3(512), C3EGeom<NT>::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL((conv3_h8<NT, C1, NT, true>), dim3((unsigned)wgs), dim3(512), C3EGeom<NT>::LDS_BYTES, stream, a);
     return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@ namespace dcscn {
 
 template <int NT>
 static hipError_t c3h16_set_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_h<NT, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NT>::LDS_BYTES);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_h<NT, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NT>::LDS_BYTES);
 }
 
 hipError_t c3h16_init_kernels() {
@@ -25,7 +25,7 @@ static hipError_t c3h16_launch_one(ConvArgs a, int n_groups, hipStream_t stream)
     const int phases = (n_groups + a.group_span - 1) / a.group_span;
     const long long ids = ((tiles + 7) / 8) * 8 * a.group_span * phases;
     if (ids > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv3_h<NT, 2, 0, true>), dim3((unsigned)ids), dim3(256), C3HGeom<NT>::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL((conv3_h<NT, 2, true>), dim3((unsigned)ids), dim3(256), C3HGeom<NT>::LDS_BYTES, stream, a);
     return hipGetLastError();
 }
 

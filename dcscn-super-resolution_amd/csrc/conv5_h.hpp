@@ -181,11 +181,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv5_h(const ConvArgs a
 
     const int n_chunks = a.n_chunks;
     dma_col(0, 0, 0);
-#ifndef C5H_ABL
-#define C5H_ABL 0          // timing-only builds (results wrong by design): 1 no fetch of the first chunk's image (the prologue a persistent kernel would hide)
-#endif
-    if constexpr ((C5H_ABL & 1) == 0) load_in(0);
-    else static_for<0, G::IN_ROUNDS>([&](auto r_) DCSCN_INL { gin[decltype(r_)::value] = f32x4{1.0f, 2.0f, 3.0f, (float)tid}; });
+    load_in(0);
     static_for<0, G::IN_ROUNDS>([&](auto r_) DCSCN_INL { convert_in(r_, 0); });
     store_in();
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
@@ -310,13 +306,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv5_h(const ConvArgs a
 //   * 16 consecutive pixels of the first / last row (columns 1 .. W - 2) or of the first / last column (rows 1 .. H - 2) of one image: the
 //     5 x 20-pixel window the 25 taps read is staged ONCE in the wave's own 12.5 KB of LDS (conv3_h's unit swizzle: conflict-free reads for
 //     all five shifts), a tap's B operand is two ds_read_b128 -- the first build fetched every tap's pixels from the tensor: 5 x the bytes
-//     through L2, 46 of its 98 us per 1024 patches (tools/fb_abl.sh);
+//     through L2, 46 of its 98 us per 1024 patches (timing-only build, since retired);
 //   * the same corner of 16 consecutive images (no window to share: every lane fetches its taps straight from the tensor).
 // A fragments come from the variant's pack_conv16 image (L2 resident), a tap row at a time; 25 taps x chunks x 3 MFMAs per job; no
 // workgroup barrier (a wave's LDS traffic is in order).  8 % of the pixels of a 48 x 48 patch, 1.5 % of a 256 x 256 image.
-#ifndef FB_ABL
-#define FB_ABL 0      // timing-only builds (tools/fb_abl.sh; results wrong by design): 1 no pixel fetches, 2 no filter fetches, 4 no stores / residual reads, 8 no MFMAs
-#endif
 constexpr int kFbWinBytes = 5 * 20 * 128;      // a job's window: 5 lines across x 20 pixels along x one 128-byte record
 struct FoldBorderJobs {             // job list of a launch (host and device)
     int segs_w, segs_h, rows_n, cols_n, j_img, cb;
@@ -392,7 +385,6 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
         }
         // the (hi | lo) units of octet kq of pixel (gi, yy, xx); ok = false: zeros
         auto fetch16 = [&](int gi, int yy, int xx, int kq, bool ok, h8& hi, h8& lo) DCSCN_INL {
-            if constexpr ((FB_ABL & 1) != 0) { u32x4 z = {0x3c003c00u, (unsigned)(ok ? xx : yy), 0x3c003c00u, 0x3c003c00u}; asm volatile("" : "+v"(z)); hi = lo = __builtin_bit_cast(h8, z); return; }
             if constexpr (IN16) {
                 // (pixels outside the image and octets past the tensor's last read the plane's zero record)
                 const unsigned off = ok && kq < rem ? 128u + (unsigned)((gi * H + yy) * W + xx) * rec + (unsigned)kq * 32u : (unsigned)kq * 32u;
@@ -434,7 +426,6 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
             h8 wh[5], wl[5], xh[5], xl[5];
 #pragma unroll
             for (int sh = 0; sh < 5; ++sh) {
-                if constexpr ((FB_ABL & 2) != 0) { u32x4 z = {0x3c003c00u, (unsigned)lane, 0x3c003c00u, 0x3c003c00u}; asm volatile("" : "+v"(z)); wh[sh] = wl[sh] = __builtin_bit_cast(h8, z); continue; }
                 const int tap = along_x ? la * 5 + sh : sh * 5 + la;                 // (wave uniform)
                 wh[sh] = *reinterpret_cast<const h8*>(fc + tap * 2048);
                 wl[sh] = *reinterpret_cast<const h8*>(fc + tap * 2048 + 1024);
@@ -454,7 +445,6 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
             }
 #pragma unroll
             for (int sh = 0; sh < 5; ++sh) {
-                if constexpr ((FB_ABL & 8) != 0) { f32x4 t = acc; const h8 a0 = wl[sh], a1 = wh[sh], b0 = xh[sh], b1 = xl[sh]; asm volatile("" : "+v"(t) : "v"(a0), "v"(a1), "v"(b0), "v"(b1)); acc = t; continue; }
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[sh], xh[sh], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sh], xl[sh], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sh], xh[sh], acc, 0, 0, 0);
@@ -472,10 +462,8 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
     if (ps == 4) {                                             // phases 4 lk .. 4 lk + 3 = HR row 4 y + lk, columns 4 x .. 4 x + 3: one 16-byte store
         const size_t idx = ((size_t)(img * H + y) * 4 + lk) * orow + (size_t)x * 4;
         f32x4 o = o4;
-        if constexpr ((FB_ABL & 4) != 0) { if (o.x == 1.2345e-30f) *reinterpret_cast<f32x4*>(yout + idx) = o; } else {
         if (a.res) o = o + *reinterpret_cast<const f32x4*>(a.res + idx);
         *reinterpret_cast<f32x4*>(yout + idx) = o;
-        }
     } else {
         const float vr[4] = {o4.x, o4.y, o4.z, o4.w};
 #pragma unroll
@@ -485,7 +473,6 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
                 const int pa = p / ps, pb = p - pa * ps;
                 const size_t idx = ((size_t)(img * H + y) * ps + pa) * orow + (size_t)(x * ps + pb);
                 float out = vr[r];
-                if constexpr ((FB_ABL & 4) != 0) { if (out == 1.2345e-30f) yout[idx] = out; continue; }
                 if (a.res) out += a.res[idx];
                 yout[idx] = out;
             }

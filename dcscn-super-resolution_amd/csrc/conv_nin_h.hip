@@ -1,6 +1,4 @@
 // conv_nin_h variants (conv_nin_h.hpp), one translation unit to parallelise the build.
-#include <cstdlib>
-
 #include "conv_nin_h.hpp"
 
 namespace dcscn {
@@ -54,9 +52,8 @@ static hipError_t nin_h_launch_one(const ConvArgs& a, int n_groups, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream) {
+hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream) {
     if (a.n_full < 1 || a.n_full > n_groups || (nt == 1 && a.n_full != n_groups) || !a.wpack16) return hipErrorInvalidValue;
-    static const bool w8 = !(getenv("DCSCN_NINH8") && getenv("DCSCN_NINH8")[0] == '0');     // (A/B aid: DCSCN_NINH8=0 keeps the 128-pixel workgroups)
     if (w8 && nt == 6 && a.in16.base && a.n_chunks >= kNinH8MinChunks && a.n_full == n_groups) return nin_h8_launch(a, n_groups, stream);
     switch (nt) {
         case 1: return nin_h_launch_one<1>(a, n_groups, stream);

@@ -3,7 +3,7 @@
 // is the full-rate K = 32 form (v_mfma_f32_16x16x16_f16 takes the same 16 cycles for half the work: profiles/r03_pipe_probe.txt).
 //
 // * 128 consecutive pixels of the flat pixel list per workgroup, wave w owns 32 of them (two MFMA column tiles) for all
-//   NT*16 <= 96 output channels of the group.  Two workgroups per CU.
+//   NT*16 <= 96 output channels of the group.  Two workgroups per CU.  (WAVES, MT = 8, 2: 256 pixels, conv_nin_h_w8.hip.)
 // * input stage = [128 pixels][8 slots of 16 bytes]: the chunk's 32 channels of each pixel, 128 contiguous bytes fetched by eight
 //   adjacent lanes of an LDS-DMA (or one source quad each with MULTI).  Slot order inside a pixel record is swizzled on the SOURCE
 //   side (the DMA destination is lane-linear): quad q = 2 kq + half sits at slot 2 * ((kq + (p >> 1)) & 3) + (half ^ (kq & 1)), which
@@ -18,30 +18,17 @@
 #include "split16.hpp"
 #include "p16.hpp"
 
-#ifndef NINH_A_NT
-#define NINH_A_NT 0        // 1: input pieces with the non-temporal policy -- measured r05: 2.91 -> 4.18 ms (the producers' lines are still on their way through L2 / MALL)
-#endif
-
-#ifndef NINH_ABL
-#define NINH_ABL 0         // tuner only (tools/ninh_abl.sh; results wrong by design): 1 no filter DMA in the K loop, 2 no MFMAs, 4 no epilogue stores, 8 no input DMA in the K loop
-#endif
-
 namespace dcscn {
 
-#ifndef NINH_WAVES
-#define NINH_WAVES 4       // waves per workgroup (tuner: 8)
-#endif
-#ifndef NINH_MT
-#define NINH_MT 2          // 16-pixel tiles per wave; pixels per workgroup = 16 * NINH_MT * NINH_WAVES (tuner: 8 waves x 1 = 128 pixels with half the serial work
-#endif                     // per wave; 8 x 2 = 256 pixels, ONE workgroup per CU, half the filter traffic per pixel)
-
-template <int NT, int S = 2>
+// WAVES: waves per workgroup; MT: 16-pixel tiles per wave; pixels per workgroup = 16 * MT * WAVES (8 x 2 = 256 pixels: ONE workgroup
+// per CU, half the filter traffic per pixel)
+template <int NT, int S = 2, int WAVES = 4, int MT_ = 2>
 struct NinHGeom {
-    static constexpr int W = NINH_WAVES;
+    static constexpr int W = WAVES;
     static constexpr int THREADS = 64 * W;
     static constexpr int KC = 32;
-    static constexpr int PIX = 16 * NINH_MT * W;
-    static constexpr int MT = NINH_MT;                        // 16-pixel tiles per wave
+    static constexpr int PIX = 16 * MT_ * W;
+    static constexpr int MT = MT_;                            // 16-pixel tiles per wave
     static constexpr int PSTRIDE = 128;
     static constexpr int A_SLOTS = PIX * 8;
     static constexpr int A_DMA = A_SLOTS / 64;                // 16 wave instructions, 4 per wave
@@ -60,9 +47,9 @@ struct NinHGeom {
 // SRC: 0 = one float32 tensor, 1 = MULTI (float32 sources through a per-quad table), 2 = P16 sources (p16.hpp) through a per-OCTET table:
 // entry = {address of the octet's hi unit in the record of pixel 0, record bytes}; the staged slot is then a ready (hi | lo) unit -- the B
 // fragments are read as they are, no split in registers.  Entries past the last octet point at a plane's zero record with stride 0.
-template <int NT, int NTV, int SRC, int S>
+template <int NT, int NTV, int SRC, int S, int WAVES, int MT>
 __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, long long pix0, int ntile) {
-    using G = NinHGeom<NT, S>;
+    using G = NinHGeom<NT, S, WAVES, MT>;
     constexpr bool MULTI = SRC != 0, IN16 = SRC == 2;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -107,8 +94,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
         constexpr int r = decltype(r_)::value;
         if constexpr (MULTI) {
             const char* src = reinterpret_cast<const char*>(((unsigned long long)ent.y << 32) | ent.x) + (unsigned long long)a_pix[r] * ent.z + (IN16 ? (dq & 1) * 16 : 0);
-            if constexpr (NINH_A_NT) glds16v_nt(src, lds0 + stage * G::A_BYTES + (unsigned)(wave + G::W * r) * 1024u);
-            else glds16v(src, lds0 + stage * G::A_BYTES + (unsigned)(wave + G::W * r) * 1024u);
+            glds16v(src, lds0 + stage * G::A_BYTES + (unsigned)(wave + G::W * r) * 1024u);
         } else {
             const int c0 = chunk * G::KC + 4 * dq;
             glds16(a_base, a_off[r] + (unsigned)((c0 < a.cin_phys ? c0 : 0) * 4), lds0 + stage * G::A_BYTES + (unsigned)(wave + G::W * r) * 1024u);
@@ -165,7 +151,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
         const unsigned Bs = b_lane + sb * G::B_STAGE;
         const unsigned An = a_lane + sn * G::A_BYTES, An2 = a_lane2 + sn * G::A_BYTES;
         // filters first, then input: the counted wait below relies on this order
-        if constexpr (!(NINH_ABL & 1)) static_for<0, G::B_ROUNDS>([&](auto r_) DCSCN_INL { dma_b(r_, cb, sb ^ 1); });
+        static_for<0, G::B_ROUNDS>([&](auto r_) DCSCN_INL { dma_b(r_, cb, sb ^ 1); });
         f32x4 na[G::MT], nb[G::MT];
         static_for<0, G::MT>([&](auto m_) DCSCN_INL {
             constexpr int m = decltype(m_)::value;
@@ -176,16 +162,13 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
                 constexpr int n = decltype(n_)::value;
                 const h8 wh = *(lds_h8_ptr)(uintptr_t)(Bs + (2 * n) * 1024);
                 const h8 wl = *(lds_h8_ptr)(uintptr_t)(Bs + (2 * n + 1) * 1024);
-                if constexpr (NINH_ABL & 2) asm volatile("" :: "v"(wh), "v"(wl), "v"(xh), "v"(xl));
-                else {
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc[m][n], 0, 0, 0);
-                }
+                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc[m][n], 0, 0, 0);
+                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc[m][n], 0, 0, 0);
+                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc[m][n], 0, 0, 0);
                 // the chunk's input pieces behind the first MFMA groups
-                if constexpr (!(NINH_ABL & 8) && m * NTV + n < G::A_ROUNDS) dma_a(std::integral_constant<int, m * NTV + n>{}, ca, sa);
+                if constexpr (m * NTV + n < G::A_ROUNDS) dma_a(std::integral_constant<int, m * NTV + n>{}, ca, sa);
             });
-            if constexpr (!(NINH_ABL & 8) && m == G::MT - 1 && G::MT * NTV < G::A_ROUNDS)
+            if constexpr (m == G::MT - 1 && G::MT * NTV < G::A_ROUNDS)
                 static_for<G::MT * NTV, G::A_ROUNDS>([&](auto r_) DCSCN_INL { dma_a(r_, ca, sa); });
             na[m] = *(lds_f32x4_ptr)(uintptr_t)(An + m * 16 * G::PSTRIDE);
             nb[m] = *(lds_f32x4_ptr)(uintptr_t)(An2 + m * 16 * G::PSTRIDE);
@@ -193,7 +176,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
         load_ent(chunk + S + 1 < last ? chunk + S + 1 : last);      // the next iteration's ca
         // the next chunk reads the fragments of chunk c + 2 and the filters of chunk c + 1: with S = 3 only this iteration's
         // input pieces (the youngest A_ROUNDS operations) may stay in flight
-        if constexpr (S == 2 || NINH_ABL != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (S == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::A_ROUNDS) : "memory");
         __syncthreads();
         static_for<0, G::MT>([&](auto m_) DCSCN_INL { xa[decltype(m_)::value] = na[decltype(m_)::value]; xb[decltype(m_)::value] = nb[decltype(m_)::value]; });
@@ -242,7 +225,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
                     v.w = activate1(v.w, av.w, act_e);
                     if (ACT_C < 0 && p < npix && chan_ok) chk[m] = nonfinite_acc(chk[m], acc[m][n], zero);
                     const u32x4 unit = p16_unit(v, m1, chk[m], zero2, p < npix && chan_ok);
-                    if (p < npix && chan_ok && (!(NINH_ABL & 4) || unit.x == 0x12345u)) *reinterpret_cast<u32x4*>(base + (size_t)p * rec) = unit;
+                    if (p < npix && chan_ok) *reinterpret_cast<u32x4*>(base + (size_t)p * rec) = unit;
                 });
             } else if (cc < owidth) {
                 static_for<0, G::MT>([&](auto m_) DCSCN_INL {
@@ -253,7 +236,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
                     v.y = activate1(v.y, av.y, act_e);
                     v.z = activate1(v.z, av.z, act_e);
                     v.w = activate1(v.w, av.w, act_e);
-                    if (p < npix && (!(NINH_ABL & 4) || v.x == 12345.678f)) {
+                    if (p < npix) {
                         chk[m] = nonfinite_acc(chk[m], acc[m][n], zero);
                         *reinterpret_cast<f32x4*>(optr + (size_t)p * ostride + ooff + cc) = v;
                     }
@@ -277,14 +260,14 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
     });
 }
 
-// grid = (pixel blocks of 128, channel groups)
-template <int NT, int SRC = 0, int S = 2, int WPS = 2>
-__global__ __launch_bounds__(64 * NINH_WAVES, (WPS * NINH_WAVES / 4) * 128 / (16 * NINH_MT * NINH_WAVES) > 0 ? (WPS * NINH_WAVES / 4) * 128 / (16 * NINH_MT * NINH_WAVES) : 1) void conv_nin_h(const ConvArgs a) {
+// grid = (pixel blocks of NinHGeom::PIX, channel groups)
+template <int NT, int SRC = 0, int S = 2, int WPS = 2, int WAVES = 4, int MT = 2>
+__global__ __launch_bounds__(64 * WAVES, (WPS * WAVES / 4) * 128 / (16 * MT * WAVES) > 0 ? (WPS * WAVES / 4) * 128 / (16 * MT * WAVES) : 1) void conv_nin_h(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const long long pix0 = (long long)blockIdx.x * NinHGeom<NT, S>::PIX;
+    const long long pix0 = (long long)blockIdx.x * NinHGeom<NT, S, WAVES, MT>::PIX;
     const int ntile = blockIdx.y;
-    if (ntile < a.n_full) conv_nin_h_body<NT, NT, SRC, S>(a, smem, pix0, ntile);          // block uniform
-    else if constexpr (NT >= 2) conv_nin_h_body<NT, NT - 1, SRC, S>(a, smem, pix0, ntile);
+    if (ntile < a.n_full) conv_nin_h_body<NT, NT, SRC, S, WAVES, MT>(a, smem, pix0, ntile);          // block uniform
+    else if constexpr (NT >= 2) conv_nin_h_body<NT, NT - 1, SRC, S, WAVES, MT>(a, smem, pix0, ntile);
 }
 
 }  // namespace dcscn

@@ -1,8 +1,6 @@
 // Winograd F(2x2,3x3) variants (conv_wino2.hpp), one translation unit to parallelise the build.
 // Built with -fno-slp-vectorize: hipcc would otherwise pair the input transform's adds into v_pk_add_f32, which costs
 // v_mov shuffles and issues worse beside MFMAs (tools/wino2_tune: 36.1 vs 35.6 ms over the 3x3 layers of the bench model).
-#include <cstdlib>
-
 #include "conv_wino2.hpp"
 
 namespace dcscn {
@@ -28,8 +26,7 @@ static hipError_t wino_launch_one(const ConvArgs& a, int n_groups, hipStream_t s
     const long long tiles = (long long)a.N * a.tiles_y * a.tiles_x;
     ConvArgs b = a;
     b.n_groups = n_groups;
-    static const int env_span = getenv("DCSCN_WINO_SPAN") ? atoi(getenv("DCSCN_WINO_SPAN")) : 0;   // tuning aid
-    b.group_span = env_span > 0 ? (env_span < n_groups ? env_span : n_groups) : wino_group_span(n_groups);
+    b.group_span = wino_group_span(n_groups);
     const int phases = (n_groups + b.group_span - 1) / b.group_span;
     const dim3 grid((unsigned)(((tiles + 7) / 8) * 8 * b.group_span * phases));      // 1-D, decoded XCD-aware in the kernel
     if (b.redo_check)                                          // behind conv3_h: 64 tile flags per workgroup (conv_wino2_redo)

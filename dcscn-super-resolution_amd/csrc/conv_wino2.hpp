@@ -27,10 +27,6 @@
 #pragma once
 #include "conv_igemm.hpp"
 
-#ifndef DCSCN_GLDS_AUX
-#define DCSCN_GLDS_AUX ""          // cache-policy suffix of the LDS-DMA loads (tuner: " nt", " sc1")
-#endif
-
 namespace dcscn {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -62,14 +58,13 @@ struct Wino2Geom {
 // compiler-reserved and is restored inside the same statement.  Completion is tracked by vmcnt; hipcc does not see the load.
 __device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
     unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" DCSCN_GLDS_AUX "\n\ts_mov_b32 m0, %0"
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "v"(voff), "s"(sbase), "s"(lds_dst)
                  : "memory");
 }
 
-// ABL (tuner only, tools/wino2_tune.hip): 0 shipped; 1 no DMA in the K loop; 2 no vmcnt wait; 3 no filter DMA; 4 no input DMA; 5 no barrier (+ no wait)
-template <int NT, int NTV, int PF, int ABL = 0>
+template <int NT, int NTV, int PF>
 __device__ __forceinline__ void conv_wino2_body(const ConvArgs& a, float* smem, int tile_id, int ntile) {
     using G = Wino2Geom<NT>;
     static_assert(PF >= 1 && PF < 16, "filter operands are read 1..15 frequencies ahead");
@@ -265,9 +260,9 @@ __device__ __forceinline__ void conv_wino2_body(const ConvArgs& a, float* smem, 
             constexpr int f = decltype(f_)::value;
             // one DMA piece behind each of the first B_ROUNDS + A_ROUNDS frequencies
             if constexpr (f >= 1 && f <= G::B_ROUNDS) {
-                if constexpr (ABL != 1 && ABL != 3) { if (more_b) dma_b(std::integral_constant<int, f - 1>{}, chunk + 1, sb ^ 1); }
+                if (more_b) dma_b(std::integral_constant<int, f - 1>{}, chunk + 1, sb ^ 1);
             } else if constexpr (f > G::B_ROUNDS && f <= G::B_ROUNDS + G::A_ROUNDS) {
-                if constexpr (ABL != 1 && ABL != 4) { if (more_a) dma_a(std::integral_constant<int, f - 1 - G::B_ROUNDS>{}, chunk + 2, sb); }
+                if (more_a) dma_a(std::integral_constant<int, f - 1 - G::B_ROUNDS>{}, chunk + 2, sb);
             }
         });
         transform(std::integral_constant<int, 1>{}, rr, v);
@@ -280,10 +275,9 @@ __device__ __forceinline__ void conv_wino2_body(const ConvArgs& a, float* smem, 
                 read_raw1(std::integral_constant<int, (2 * (f - 8) + 1) / 4>{}, std::integral_constant<int, (2 * (f - 8) + 1) % 4>{}, be, bo, rr);
             }
         });
-        if constexpr (ABL != 2 && ABL != 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (ABL != 5) __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
     }
-    if constexpr (ABL == 2 || ABL == 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     // ---- output transform (wave-local) + epilogue: identical to conv_wino ----
     const int gy0 = y0 + 2 * tr;
@@ -368,7 +362,7 @@ __device__ __forceinline__ void conv_wino2_body(const ConvArgs& a, float* smem, 
 }
 
 // launch_bounds' second argument is waves per SIMD = resident 4-wave workgroups per CU
-template <int NT, int WPS = 2, int PF = 3, int ABL = 0>
+template <int NT, int WPS = 2, int PF = 3>
 __global__ __launch_bounds__(256, WPS) void conv_wino2(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // XCD-aware decode of the 1-D grid (see conv_wino): the channel groups of one pixel tile get ids that are congruent
@@ -386,8 +380,8 @@ __global__ __launch_bounds__(256, WPS) void conv_wino2(const ConvArgs a) {
     const int tile_id = q * 8 + (r & 7);
     if (tile_id >= a.N * a.tiles_y * a.tiles_x) return;
     if (a.redo_check && (a.redo[0] == 0 || a.redo[1 + tile_id / (a.tiles_y * a.tiles_x)] == 0)) return;   // float32 plan: flagged images only
-    if (ntile < a.n_full) conv_wino2_body<NT, NT, PF, ABL>(a, smem, tile_id, ntile);                 // block uniform
-    else if constexpr (NT >= 2) conv_wino2_body<NT, NT - 1, PF, ABL>(a, smem, tile_id, ntile);
+    if (ntile < a.n_full) conv_wino2_body<NT, NT, PF>(a, smem, tile_id, ntile);                 // block uniform
+    else if constexpr (NT >= 2) conv_wino2_body<NT, NT - 1, PF>(a, smem, tile_id, ntile);
 }
 
 // The launch behind conv3_h (split16.hpp): recompute in f32 the pixel tiles whose redo flag is set -- normally none.  A full grid
@@ -412,8 +406,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino2_redo(const ConvArgs a) {
         for (int ntile = 0; ntile < a.n_groups; ++ntile) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // clamped DMAs of the previous body
             __syncthreads();
-            if (ntile < a.n_full) conv_wino2_body<NT, NT, PF, 0>(a, smem, tile_id, ntile);
-            else if constexpr (NT >= 2) conv_wino2_body<NT, NT - 1, PF, 0>(a, smem, tile_id, ntile);
+            if (ntile < a.n_full) conv_wino2_body<NT, NT, PF>(a, smem, tile_id, ntile);
+            else if constexpr (NT >= 2) conv_wino2_body<NT, NT - 1, PF>(a, smem, tile_id, ntile);
         }
     }
 }

@@ -224,29 +224,7 @@ int launch_op(dcscn_ctx* h, const Op& op, int nb, int H, int W, const float* x, 
         a.n_jobs = (int)(cols * a.n_blocks);
         a.jobs_per_wg = (a.n_jobs + 255) / 256;
         const int grid = (a.n_jobs + a.jobs_per_wg - 1) / a.jobs_per_wg;
-#ifdef STREAM_DBG                              // timing-probe builds only (tools/stream_dbg.sh): shader clocks of workgroup 0 to a file
-        static long long* dbg = nullptr;
-        if (getenv("DCSCN_STREAM_DBG")) {
-            if (!dbg) HIP_TRY(h, hipMalloc((void**)&dbg, 16 * 64 * 4 * sizeof(long long)));
-            HIP_TRY(h, hipMemsetAsync(dbg, 0, 16 * 64 * 4 * sizeof(long long), stream));
-            a.dbg = dbg;
-        }
-#endif
         HIP_TRY(h, stream_launch(a, grid, stream16, stream));
-#ifdef STREAM_DBG
-        if (a.dbg) {
-            std::vector<long long> host(16 * 64 * 4);
-            HIP_TRY(h, hipStreamSynchronize(stream));
-            HIP_TRY(h, hipMemcpy(host.data(), dbg, host.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            FILE* f = fopen(getenv("DCSCN_STREAM_DBG"), "w");
-            if (f) {
-                for (int w = 0; w < 2 * a.L + 1; ++w)
-                    for (int t = 0; t < 64; ++t)
-                        fprintf(f, "%d %d %d %lld %lld %lld %lld\n", w, (int)a.role[w], t, host[(w * 64 + t) * 4], host[(w * 64 + t) * 4 + 1], host[(w * 64 + t) * 4 + 2], host[(w * 64 + t) * 4 + 3]);
-                fclose(f);
-            }
-        }
-#endif
         return DCSCN_OK;
     }
     if (op.kind == OP_DW) {
@@ -351,7 +329,7 @@ int launch_op(dcscn_ctx* h, const Op& op, int nb, int H, int W, const float* x, 
             OutDesc& o = i == 0 ? b.out0 : b.out1;
             if (op.out_buf[i] >= 0 && h->bufs[op.out_buf[i]].p16) o.p16 = p16_desc(h, op.out_buf[i]);
         }
-        if (op.shape.nin) HIP_TRY(h, nin_h_launch(op.h16.nt, b, op.h16.n_tiles, stream));
+        if (op.shape.nin) HIP_TRY(h, nin_h_launch(op.h16.nt, b, op.h16.n_tiles, h->nin_h8, stream));
         else if (op.fold_s > 0) {
             b.bias = op.h16.d_bias;
             HIP_TRY(h, c5h_launch(op.h16.nt, b, stream));
@@ -592,6 +570,7 @@ int run_forward(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, 
     gkey.split16 = h->split16 ? h->split16_mask : 0;
     gkey.nb = nb;                                        // the pass size (sub_batch_pixels / budget) shapes the launch sequence too
     gkey.h8 = h->conv3_h8 ? 1 : 0;
+    gkey.nin_h8 = h->nin_h8 ? 1 : 0;
     gkey.p16 = h->p16_now ? 1 : 0;
     gkey.carve = (unsigned long long)h->carve_gen;
     const bool graphs = h->graph_replay && !h->profile && !h->debug_digest && !h->debug_poison;   // (debug launches allocate / are not part of the key)

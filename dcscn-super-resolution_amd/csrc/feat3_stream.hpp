@@ -22,22 +22,7 @@
 #include "feat_stream.hpp"
 #include "p16.hpp"
 
-#ifndef S3_ABL
-#define S3_ABL 0           // tools/s3_abl.sh: timing-only builds (results wrong by design): 1 no MFMAs, 2 no ring reads, 4 no global stores, 8 no CNN1 arithmetic,
-                           // 16 no epilogue arithmetic (PReLU / split / swap), 32 no ring stores, 64 no workgroup barrier, 128 no loads of the input image
-#endif
-
 namespace dcscn {
-
-// (ring stores and the step's barrier through wrappers: the timing-only builds of tools/s3_abl.sh take them out)
-__device__ __forceinline__ void s3_st(unsigned addr, f32x4 v) {
-    if constexpr ((S3_ABL & 32) != 0) asm volatile("" ::"v"(v), "v"(addr));
-    else stream_st(addr, v);
-}
-__device__ __forceinline__ void s3_barrier() {
-    if constexpr ((S3_ABL & 64) != 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else stream_barrier();
-}
 
 __device__ __forceinline__ StreamArgs s3_geometry(const Stream3Args& a) {
     StreamArgs g{};                                            // stream_row only looks at the job geometry
@@ -66,7 +51,6 @@ __device__ __forceinline__ S3RowOut s3_row_out(const S3Out& o, const StreamRow& 
 // tile n, lane group q: P16 unit 4 n + q of the record (octet 2 n + (q >> 1), part q & 1); float32: channels 16 n + 4 q ..  A destination stores the
 // writer's conv channels [lo, hi) only (B2 writes octet 0 of Concat2, the A1 || B1 waves octets 1 .. 3); none: both pointers null
 __device__ __forceinline__ void s3_store_global(const S3Out& o, const S3RowOut& ro, int col, int n, int q, const u32x4 unit, const f32x4 v) {
-    if constexpr ((S3_ABL & 4) != 0) return;
     const unsigned off = (unsigned)col * ro.rec + (unsigned)(n * 64 + q * 16);
     if (ro.p16) {
         const int c8 = 8 * (2 * n + (q >> 1));
@@ -103,7 +87,6 @@ __device__ __forceinline__ void s3_first_role(const Stream3Args& a, const Stream
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const int cx = ri.sx + 3 * j + k - 1;
-            if constexpr ((S3_ABL & 128) != 0) dst[k] = (float)(cx & 7); else
             dst[k] = live && cx >= 0 && cx < a.W ? row[cx] : 0.0f;
         }
     };
@@ -112,9 +95,6 @@ __device__ __forceinline__ void s3_first_role(const Stream3Args& a, const Stream
     load_row(0, xw[0]);
     load_row(1, xw[1]);
     load_row(2, xw[2]);
-#ifdef S3_DBG
-    long long dbg_c = 0, dbg_b = 0, dbg_t = __builtin_readcyclecounter();
-#endif
     auto step = [&](auto p_, int t) DCSCN_INL {
         constexpr int p = decltype(p_)::value;                // t mod 5
         const int g = t;
@@ -137,26 +117,18 @@ __device__ __forceinline__ void s3_first_role(const Stream3Args& a, const Stream
 #pragma unroll
                     for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                        for (int dx = 0; dx < 3; ++dx) if (!(S3_ABL & 8) || (dy == 1 && dx == 1)) s += w9[n][dy * 3 + dx] * xw[(p + 4 + dy) % 5][m + dx];
+                        for (int dx = 0; dx < 3; ++dx) s += w9[n][dy * 3 + dx] * xw[(p + 4 + dy) % 5][m + dx];
                     f32x4 v = stream_prelu(bs[n] + s, al[n]);
                     v = ok ? v : kStreamZero;
                     const u32x4 unit = p16_unit(v, m1, chk, zero2);
                     if (to_global && ri.store && cx >= ri.ux0 && cx < ri.ux1) s3_store_global(a.out[0], ro, 3 * j + m, n, q, unit, v);
                     // (four ring slots: row g goes to its slot while CNN2 reads rows g-3 .. g-1; ONE barrier per step)
-                    if (2 * n + (q >> 1) < a.first_out.octs) s3_st(wb + (unsigned)m * out_px + (unsigned)n * 64u, __builtin_bit_cast(f32x4, unit));
+                    if (2 * n + (q >> 1) < a.first_out.octs) stream_st(wb + (unsigned)m * out_px + (unsigned)n * 64u, __builtin_bit_cast(f32x4, unit));
                 }
             }
             if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + ri.img] = 1; }
         }
-#ifdef S3_DBG
-        const long long tb = __builtin_readcyclecounter();
-        dbg_c += tb - dbg_t;
-#endif
-        s3_barrier();
-#ifdef S3_DBG
-        dbg_t = __builtin_readcyclecounter();
-        dbg_b += dbg_t - tb;
-#endif
+        stream_barrier();
     };
     for (int t = 0; t < T; t += 5) {
         step(std::integral_constant<int, 0>{}, t);
@@ -165,9 +137,6 @@ __device__ __forceinline__ void s3_first_role(const Stream3Args& a, const Stream
         if (t + 3 < T) step(std::integral_constant<int, 3>{}, t + 3);
         if (t + 4 < T) step(std::integral_constant<int, 4>{}, t + 4);
     }
-#ifdef S3_DBG
-    if (a.dbg && blockIdx.x == 0 && lane == 0) { long long* d = a.dbg + (threadIdx.x >> 6) * 4; d[0] = dbg_c; d[1] = dbg_b; d[2] = T; }
-#endif
 }
 
 // ---- CNN2 .. CNNL (and B2): a 3x3 conv (NT 16-channel output tiles) from the predecessor's ring ---------------------------------
@@ -263,17 +232,9 @@ __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamA
                 h8 xh[kStreamMT], xl[kStreamMT];
 #pragma unroll
                 for (int m = 0; m < kStreamMT; ++m) {
-                    if constexpr ((S3_ABL & 2) != 0) { u32x4 z = {0x3c003c00u, 0x3c003c00u, base, 0x3c003c00u}; asm volatile("" : "+v"(z)); xh[m] = xl[m] = __builtin_bit_cast(h8, z); } else {
                     xh[m] = __builtin_bit_cast(h8, stream_ld(base + (unsigned)m * IN_PX));
                     xl[m] = __builtin_bit_cast(h8, stream_ld(base + (unsigned)m * IN_PX + 16u));
-                    }
                 }
-                if constexpr ((S3_ABL & 1) != 0) {
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-#pragma unroll
-                        for (int m = 0; m < kStreamMT; ++m) { if (s == 0) acc[m][n] = r.bs[n]; f32x4 tt = acc[m][n]; const h8 fa = r.fh[s][n], fb = r.fl[s][n], xa = xh[m], xb = xl[m]; asm volatile("" : "+v"(tt) : "v"(xa), "v"(xb), "v"(fa), "v"(fb)); acc[m][n] = tt; }
-                } else
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
 #pragma unroll
@@ -293,9 +254,8 @@ __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamA
                 const int cx = ri.sx + 3 * j + m;
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    f32x4 v = (S3_ABL & 16) ? acc[m][n] : stream_prelu(acc[m][n] * c.inv, r.am1[n]);
+                    f32x4 v = stream_prelu(acc[m][n] * c.inv, r.am1[n]);
                     v = cx >= 0 && cx < a.W ? v : kStreamZero;      // SAME padding: columns outside the image are zero in every ring
-                    if constexpr ((S3_ABL & 16) != 0) unit[m][n] = __builtin_bit_cast(u32x4, v); else
                     unit[m][n] = p16_unit(v, m1, chk, zero2);
                     if (to_global && ri.store && cx >= ri.ux0 && cx < ri.ux1) s3_store_global(og, ro, 3 * j + m, n, q, unit[m][n], v);
                 }
@@ -309,7 +269,7 @@ __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamA
         for (int n = 0; n < NT; ++n)
             if (2 * n + (q >> 1) < c.out.octs) {
 #pragma unroll
-                for (int m = 0; m < kStreamMT; ++m) s3_st(wb + (unsigned)m * out_px + (unsigned)n * 64u, zero_row ? kStreamZero : __builtin_bit_cast(f32x4, unit[m][n]));
+                for (int m = 0; m < kStreamMT; ++m) stream_st(wb + (unsigned)m * out_px + (unsigned)n * 64u, zero_row ? kStreamZero : __builtin_bit_cast(f32x4, unit[m][n]));
             }
     }
 }
@@ -319,24 +279,10 @@ __device__ __forceinline__ void s3_conv_role(const Stream3Args& a, const StreamA
     s3_conv_load<OCTS, NT>(a, ci, lane, r);
     const float m1 = opaque_minus_one();
     const h2 zero2 = p16_opaque_zero2();
-#ifdef S3_DBG
-    long long dbg_c = 0, dbg_b = 0, dbg_t = __builtin_readcyclecounter();
-#endif
     for (int t = 0; t < T; ++t) {
         s3_conv_step<OCTS, NT>(a, geo, ci, lds0, j0, rows, t, lane, r, m1, zero2);
-#ifdef S3_DBG
-        const long long tb = __builtin_readcyclecounter();
-        dbg_c += tb - dbg_t;
-#endif
-        s3_barrier();
-#ifdef S3_DBG
-        dbg_t = __builtin_readcyclecounter();
-        dbg_b += dbg_t - tb;
-#endif
+        stream_barrier();
     }
-#ifdef S3_DBG
-    if (a.dbg && blockIdx.x == 0 && lane == 0) { long long* d = a.dbg + (threadIdx.x >> 6) * 4; d[0] = dbg_c; d[1] = dbg_b; d[2] = T; }
-#endif
 }
 
 // ---- two light convs in ONE wave (nin.on: A1 || B1 takes two waves of the eight): they compute different stream rows of the same step, one
@@ -349,25 +295,11 @@ __device__ __forceinline__ void s3_pair_role(const Stream3Args& a, const StreamA
     s3_conv_load<O2, 1>(a, c2, lane, r2);
     const float m1 = opaque_minus_one();
     const h2 zero2 = p16_opaque_zero2();
-#ifdef S3_DBG
-    long long dbg_c = 0, dbg_b = 0, dbg_t = __builtin_readcyclecounter();
-#endif
     for (int t = 0; t < T; ++t) {
         s3_conv_step<O1, 1>(a, geo, c1, lds0, j0, rows, t, lane, r1, m1, zero2);
         s3_conv_step<O2, 1>(a, geo, c2, lds0, j0, rows, t, lane, r2, m1, zero2);
-#ifdef S3_DBG
-        const long long tb = __builtin_readcyclecounter();
-        dbg_c += tb - dbg_t;
-#endif
-        s3_barrier();
-#ifdef S3_DBG
-        dbg_t = __builtin_readcyclecounter();
-        dbg_b += dbg_t - tb;
-#endif
+        stream_barrier();
     }
-#ifdef S3_DBG
-    if (a.dbg && blockIdx.x == 0 && lane == 0) { long long* d = a.dbg + (threadIdx.x >> 6) * 4; d[0] = dbg_c; d[1] = dbg_b; d[2] = T; }
-#endif
 }
 
 // ---- A1 || B1 (nin.on): the 1x1 GEMM over the concat of all L layers, accumulated as the layers' rows appear -- H_concat never exists, no
@@ -380,12 +312,9 @@ template <int L>
 __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamArgs& geo, int n, unsigned lds0, int j0, int rows, int T, int lane) {
     constexpr int R = 2 * L - 1;
     const int j = lane & 15, q = lane >> 4;
-#ifndef S3_NIN_PRIO
-#define S3_NIN_PRIO 1
-#endif
     // this wave's step is seven short dependent blocks (ring reads -> nine MFMAs): behind its SIMD partner's bursts of 27 - 54 MFMAs each of them
     // would wait; with priority its few MFMAs go first and the partner loses nothing it can measure
-    if (S3_NIN_PRIO) asm volatile("s_setprio 1");
+    asm volatile("s_setprio 1");
     h8 fh[L], fl[L];
     {
         const char* wsrc = reinterpret_cast<const char*>(a.blob + a.nin.w_off);
@@ -402,9 +331,6 @@ __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamAr
     const unsigned b1_px = (unsigned)a.nin.b1.px, b1_row = (unsigned)kStreamRowPx * b1_px;
     f32x4 acc[R][kStreamMT];
     StreamCursor cur;
-#ifdef S3_DBG
-    long long dbg_c = 0, dbg_b = 0, dbg_t = __builtin_readcyclecounter();
-#endif
     auto step = [&](auto p_, int t) DCSCN_INL {
         constexpr int p = decltype(p_)::value;                     // t mod R
         static_for<0, L>([&](auto i_) DCSCN_INL {
@@ -450,28 +376,17 @@ __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamAr
                 v = !ri.zero && cx >= 0 && cx < a.W ? v : kStreamZero;      // SAME padding for B2: zero rows and columns outside the image are zeros in the ring
                 const u32x4 unit = p16_unit(v, m1, chk, zero2);
                 if (!ri.zero && ri.store && cx >= ri.ux0 && cx < ri.ux1) s3_store_global(a.out2, ro, 3 * j + m, n, q, unit, v);
-                if (n == 0 && q < 2) s3_st(wb + (unsigned)m * b1_px, __builtin_bit_cast(f32x4, unit));      // B1 = channels 0 .. 7: the octet's hi and lo units
+                if (n == 0 && q < 2) stream_st(wb + (unsigned)m * b1_px, __builtin_bit_cast(f32x4, unit));      // B1 = channels 0 .. 7: the octet's hi and lo units
             }
             if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + ri.img] = 1; }
         }
-#ifdef S3_DBG
-        const long long tb = __builtin_readcyclecounter();
-        dbg_c += tb - dbg_t;
-#endif
-        s3_barrier();
-#ifdef S3_DBG
-        dbg_t = __builtin_readcyclecounter();
-        dbg_b += dbg_t - tb;
-#endif
+        stream_barrier();
     };
     for (int t = 0; t < T; t += R)
         static_for<0, R>([&](auto p_) DCSCN_INL {
             constexpr int p = decltype(p_)::value;
             if (t + p < T) step(p_, t + p);
         });
-#ifdef S3_DBG
-    if (a.dbg && blockIdx.x == 0 && lane == 0) { long long* d = a.dbg + (threadIdx.x >> 6) * 4; d[0] = dbg_c; d[1] = dbg_b; d[2] = T; }
-#endif
 }
 
 // one workgroup = n_waves <= 8 waves (CNN1 + one per conv; pack.hip: the role table), one per CU (the rings take most of the LDS)
@@ -498,11 +413,7 @@ __global__ __launch_bounds__(512) void feat3_stream(const Stream3Args a) {
         //  pair 1 = conv[L - 4] reading three octets and B2 = conv[L - 1] reading B1's one)
         if (ci == kS3RolePair) s3_pair_role<2, 2>(a, geo, a.L - 3, a.L - 2, lds0, j0, rows, T, lane);
         else s3_pair_role<3, 1>(a, geo, a.L - 4, a.L - 1, lds0, j0, rows, T, lane);
-#ifndef S3_NO_NIN
     } else if (ci >= kS3RoleNin) s3_nin_role<7>(a, geo, ci - kS3RoleNin, lds0, j0, rows, T, lane);
-#else
-    } else if (ci >= kS3RoleNin) { }
-#endif
     else {
         const bool two = a.conv[ci].tiles == 2;
         switch (a.conv[ci].in.octs) {

@@ -36,12 +36,6 @@
 #pragma once
 #include "conv_igemm.hpp"
 
-#ifndef STREAM_ABL
-#define STREAM_ABL 0      // tools/stream_abl.sh: timing-only builds with one cost removed (results wrong by design); 1 = no MFMA in the
-                          // separable convs (4 VALU FMAs per tile instead), 15 = no MFMA anywhere (A1 || B1 waves too): a bound for ANY faster matrix instruction,
-                          // 16 = PROJECTION of a split16 variant: per two 16-channel chunks the 8 NT v_mfma_f32_16x16x4_f32 are replaced by the hi / lo
-                          // split of the B values (12 VALU per pixel tile) and 3 NT v_mfma_f32_16x16x32_f16 on stand-in A operands (finite bit patterns)
-#endif
 #include "split16.hpp"
 
 namespace dcscn {
@@ -51,16 +45,6 @@ typedef __attribute__((address_space(3))) f32x4* stream_lds_wr;
 
 __device__ __forceinline__ void stream_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifdef STREAM_DBG
-// timing probe: workgroup 0 records the shader clock at four points of steps 64..127 per wave
-#define STREAM_STAMP(a, t, k)                                                                                     \
-    do {                                                                                                          \
-        if ((a).dbg && blockIdx.x == 0 && (t) >= 64 && (t) < 128 && (threadIdx.x & 63) == 0)                        \
-            (a).dbg[((threadIdx.x >> 6) * 64 + ((t) - 64)) * 4 + (k)] = clock64();                                 \
-    } while (0)
-#else
-#define STREAM_STAMP(a, t, k) do { } while (0)
-#endif
 __device__ __forceinline__ f32x4 stream_ld(unsigned addr) { return *(stream_lds_rd)(uintptr_t)addr; }
 __device__ __forceinline__ void stream_st(unsigned addr, f32x4 v) { *(stream_lds_wr)(uintptr_t)addr = v; }
 
@@ -154,7 +138,7 @@ __device__ __forceinline__ void stream_first_role(const StreamArgs& a, unsigned 
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const int cx = ri.sx + 3 * j + k - 1;
-            dst[k] = live && cx >= 0 && cx < a.W && STREAM_ABL != 7 && STREAM_ABL != 8 ? row[cx] : 0.0f;
+            dst[k] = live && cx >= 0 && cx < a.W ? row[cx] : 0.0f;
         }
     };
 #pragma unroll
@@ -162,7 +146,6 @@ __device__ __forceinline__ void stream_first_role(const StreamArgs& a, unsigned 
     load_row(0, xw[2]);
     load_row(1, xw[3]);
     for (int t = 0; t < T; ++t) {
-        STREAM_STAMP(a, t, 0);
         const int g = t;
 #pragma unroll
         for (int s = 0; s < 3; ++s)
@@ -190,9 +173,7 @@ __device__ __forceinline__ void stream_first_role(const StreamArgs& a, unsigned 
                 }
             }
         }
-        STREAM_STAMP(a, t, 1);
         stream_barrier();
-        STREAM_STAMP(a, t, 2);
         if (live) {
             const unsigned wb = lds0 + a.first_out.off + (((unsigned)(g % 3) * kStreamRowPx + 3 * j + 1) * a.first_out.units + q) * 16u;
 #pragma unroll
@@ -201,7 +182,6 @@ __device__ __forceinline__ void stream_first_role(const StreamArgs& a, unsigned 
                 for (int n = 0; n < 2; ++n)
                     if (n * 4 + q < a.first_out.quads) stream_st(wb + (unsigned)(m * a.first_out.units + n * 4) * 16u, v[m][n]);
         }
-        STREAM_STAMP(a, t, 3);
         stream_barrier();
     }
 }
@@ -243,9 +223,6 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
     constexpr int CH = (QUADS + 3) / 4;
     constexpr unsigned PX = (unsigned)(QUADS | 1) * 16u;
     f32x4 dpair[F16 ? MT : 1];                                // F16: the first chunk of a pair waits here for the second
-#if STREAM_ABL == 16
-    f32x4 dkeep[MT];
-#endif
     static_for<0, CH>([&](auto ch_) DCSCN_INL {
         constexpr int ch = decltype(ch_)::value;
         constexpr int QL = ch == CH - 1 ? QUADS - 4 * (CH - 1) : 4;
@@ -265,9 +242,9 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
             constexpr int dy = decltype(dy_)::value, b = decltype(b_)::value;
             const unsigned xb = rowb[dy] + qoff;
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) dw[b][dx] = STREAM_ABL == 4 ? f32x4{1.0f, 2.0f, 3.0f, (float)dx} : stream_ld(dwb + (unsigned)((dy * 3 + dx) * QUADS) * 16u);
+            for (int dx = 0; dx < 3; ++dx) dw[b][dx] = stream_ld(dwb + (unsigned)((dy * 3 + dx) * QUADS) * 16u);
 #pragma unroll
-            for (int k = 0; k < MT + 2; ++k) xv[b][k] = STREAM_ABL == 3 ? f32x4{(float)k, (float)lane, 1.0f, 2.0f} : stream_ld(xb + (unsigned)k * PX);
+            for (int k = 0; k < MT + 2; ++k) xv[b][k] = stream_ld(xb + (unsigned)k * PX);
         };
         auto mult = [&](auto b_, auto first_) DCSCN_INL {
             constexpr int b = decltype(b_)::value;
@@ -277,7 +254,6 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     if (first && dx == 0) d[m] = dw[b][dx] * xv[b][m + dx];
-                    else if (STREAM_ABL == 2) { if (dx == 1) d[m] += xv[b][m + dx] + dw[b][dx]; }
                     else d[m] += dw[b][dx] * xv[b][m + dx];
                 }
             asm volatile("" ::: "memory");
@@ -349,28 +325,6 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
                 }
             }
         } else {
-#if STREAM_ABL == 16
-        if constexpr ((ch & 1) == 0 && ch != CH - 1) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m) dkeep[m] = d[m];
-        } else {
-            const float m1 = opaque_minus_one();
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                h8 bh, bl;
-                if constexpr ((ch & 1) != 0) split8(dkeep[m], d[m], m1, bh, bl); else split8(d[m], d[m], m1, bh, bl);
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    const u32x4 wu = __builtin_bit_cast(u32x4, wp[n]) & 0x3fff3fffu;      // a finite f16 pattern (timing only)
-                    const h8 ah = __builtin_bit_cast(h8, wu);
-                    f32x4 c0 = ch <= 1 ? init[n] : acc[m][n];
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c0, 0, 0, 0);
-                    c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c0, 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c0, 0, 0, 0);
-                }
-            }
-        }
-#else
 #pragma unroll
         for (int s = 0; s < K::STEPS; ++s)
 #pragma unroll
@@ -378,11 +332,9 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
                 const float bv = K::pick(d[m], s, q);
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    if (STREAM_ABL == 1 || STREAM_ABL == 15) { if (s == 0) acc[m][n] = (ch == 0 ? init[n] : acc[m][n]) + d[m] * wp[n]; }
-                    else acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[n][s], bv, ch == 0 && s == 0 ? init[n] : acc[m][n], 0, 0, 0);
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[n][s], bv, ch == 0 && s == 0 ? init[n] : acc[m][n], 0, 0, 0);
                 }
             }
-#endif
         }
     });
 }
@@ -396,12 +348,11 @@ __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const Stre
     constexpr unsigned in_px = (unsigned)(QUADS | 1) * 16u, in_row = (unsigned)kStreamRowPx * in_px;
     StreamCursor cur;
     for (int t = 0; t < T; ++t) {
-        STREAM_STAMP(a, t, 0);
         const int g = t - c.lag;
         const bool live = g >= 0 && g < rows;
         f32x4 acc[kStreamMT][NT];
         bool zero_row = true;               // separator / outside the image: the ring gets zeros
-        if (live && STREAM_ABL != 5 && STREAM_ABL != 8) {
+        if (live) {
             const StreamRow ri = stream_row(a, j0, cur, g);
             zero_row = ri.zero;
             if (!ri.zero) {
@@ -444,9 +395,7 @@ __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const Stre
                 }
             }
         }
-        STREAM_STAMP(a, t, 1);
         stream_barrier();
-        STREAM_STAMP(a, t, 2);
         if (live && !c.to_global) {
             const unsigned wb = lds0 + c.out.off + (((unsigned)(g % 3) * kStreamRowPx + 3 * j + 1) * c.out.units + q) * 16u;
 #pragma unroll
@@ -458,7 +407,6 @@ __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const Stre
                         else stream_st(wb + (unsigned)(m * c.out.units + n * 4) * 16u, acc[m][n]);
                     }
         }
-        STREAM_STAMP(a, t, 3);
         stream_barrier();
     }
 }
@@ -483,7 +431,6 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
     if (l == 0) l = L;
     auto step = [&](auto p_, int t) DCSCN_INL {
         constexpr int p = decltype(p_)::value;
-        STREAM_STAMP(a, t, 0);
         // (opaque per step: otherwise every lane-derived address of every branch is hoisted out of the loop and spilled)
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));
@@ -492,17 +439,12 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
         const int g = t + 1 - 2 * l;                   // parity of g = parity of t + 1 = p
         const bool live = g >= 0 && g < rows;
         const bool last = l == L;
-        if (live && STREAM_ABL != 6 && STREAM_ABL != 8) {
+        if (live) {
             const StreamNinSrc& s = a.nin[l - 1];
             {
                 const StreamRow ri = stream_row(a, j0, cur[p], g);
                 if (!ri.zero) {
                     const unsigned rowb = lds0 + s.ring.off + ((unsigned)(g % 3) * kStreamRowPx + 3 * j + 1) * (unsigned)s.ring.units * 16u;
-#if STREAM_ABL == 16
-                    f32x4 xkeep[kStreamMT];
-#pragma unroll
-                    for (int m = 0; m < kStreamMT; ++m) xkeep[m] = f32x4{1.0f, 2.0f, 3.0f, 4.0f};
-#endif
                     if constexpr (F16) {
                         // chunk pairs on v_mfma_f32_16x16x32_f16, an odd last chunk on the K = 16 form (stream_dw_pw, F16); a short last
                         // chunk's missing quads read a valid one against zero filter rows
@@ -574,41 +516,15 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
                                 xv[m].y = e1;
                             }
                         }
-#if STREAM_ABL == 16
-                        if ((ch & 1) == 0 && ch != s.chunks - 1) {
-#pragma unroll
-                            for (int m = 0; m < kStreamMT; ++m) xkeep[m] = xv[m];
-                        } else {
-                            const float m1 = opaque_minus_one();
-                            const h8 a0 = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, w0) & 0x3fff3fffu);
-                            const h8 a1 = __builtin_bit_cast(h8, __builtin_bit_cast(u32x4, w1) & 0x3fff3fffu);
-#pragma unroll
-                            for (int m = 0; m < kStreamMT; ++m) {
-                                h8 bh, bl;
-                                split8(xkeep[m], xv[m], m1, bh, bl);
-                                f32x4 c0 = acc[p][m][0], c1 = acc[p][m][1];
-                                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bh, c0, 0, 0, 0);
-                                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bh, c1, 0, 0, 0);
-                                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bl, c0, 0, 0, 0);
-                                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bl, c1, 0, 0, 0);
-                                acc[p][m][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bh, c0, 0, 0, 0);
-                                acc[p][m][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bh, c1, 0, 0, 0);
-                            }
-                        }
-#else
 #pragma unroll
                         for (int k = 0; k < 4; ++k)
                             if (k < steps) {
 #pragma unroll
                                 for (int m = 0; m < kStreamMT; ++m) {
-                                    if (STREAM_ABL == 15) { if (k == 0) { acc[p][m][0] += w0 * xv[m]; acc[p][m][1] += w1 * xv[m]; } }
-                                    else {
                                     acc[p][m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[k], xv[m][k], acc[p][m][0], 0, 0, 0);
                                     acc[p][m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[k], xv[m][k], acc[p][m][1], 0, 0, 0);
-                                    }
                                 }
                             }
-#endif
                     }
                 }
                 if (last) {
@@ -638,10 +554,7 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
                 }
             }
         }
-        STREAM_STAMP(a, t, 1);
         stream_barrier();
-        STREAM_STAMP(a, t, 2);
-        STREAM_STAMP(a, t, 3);
         stream_barrier();
     };
     for (int t = 0; t < T; t += 2) {

@@ -130,7 +130,8 @@ hipError_t nin_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t strea
 // a multi-source table holds 8 entries per chunk and every entry points at readable memory (invalid ones with stride 0).
 constexpr int kNinHKC = 32;
 hipError_t nin_h_init_kernels();
-hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream);
+// w8 (option "nin_h8"): launches with P16 sources, six tiles, every group full and K >= 1024 take 256-pixel workgroups (conv_nin_h_w8.hip)
+hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream);
 // conv3_h.hpp: 3x3 conv + bias + activator (+ depth_to_space) as a direct implicit GEMM; `nt` tiles per group (1..5), groups as for
 // wino_launch; args.wpack16 = pack_conv16 image with 9 taps, args.n_chunks = ceil(cin_phys / 32), args.redo (one flag per 16x16 tile)
 constexpr int kC3hKC = 32;
@@ -196,8 +197,9 @@ struct StreamArgs {
     int32_t n_blocks, useful_h, rows_c;    // row block b computes rows_c rows from b * useful_h - halo (0 when n_blocks == 1)
     int32_t n_jobs, jobs_per_wg;
     int32_t L, n_conv, total_lag;
-    long long* dbg;                        // timing probe (STREAM_DBG builds, tools/stream_abl.sh): [wave][step][4] shader clocks of workgroup 0
-    int8_t role[16];                       // wave -> 0: CNN1, 1 .. n_conv: conv[role - 1], 16 + i: A1 || B1 row slot i (balanced over the 4 SIMDs)
+    // wave -> 0: CNN1, 1 .. n_conv: conv[role - 1], 16 + i: A1 || B1 row slot i (balanced over the 4 SIMDs).  16-byte aligned: the
+    // fields behind it keep the alignment the kernels' merged scalar loads were built with
+    alignas(16) int8_t role[16];
     int32_t ring_bytes, ldsw_bytes, ldsw_src;   // LDS image: [0, ring_bytes) zero, then ldsw_bytes copied from blob + ldsw_src
     int32_t first_w;                       // blob offset of CNN1: depthwise[9 (+3)], pointwise[32], bias[32], slope[32]
     StreamRing first_out;
@@ -273,7 +275,6 @@ struct Stream3Args {
     int32_t L, total_lag, n_waves;
     int8_t role_conv[kS3MaxWaves]; // wave -> -1: CNN1, 0 .. L - 2: that conv (0 = CNN2); with nin.on also kS3RolePair + 0 (conv[L - 3] and conv[L - 2] in one wave),
                                    // kS3RolePair + 1 (conv[L - 4] and B2 = conv[L - 1]) and kS3RoleNin + n (A1 || B1, output tile n)
-    int8_t role_tile[kS3MaxWaves]; // (unused)
     int32_t first_w;               // blob offset of CNN1: filter [9][32], bias [32], slope - 1 [32]
     S3Ring first_out;
     S3Conv conv[kS3MaxL];
@@ -282,7 +283,6 @@ struct Stream3Args {
     S3Out out2;                    // nin.on: Concat2 [B2 | A1], channels [8, 32) written by the A1 || B1 waves
     int32_t ring_bytes;
     int32_t* redo;                 // [0] pass flag, [1 + image] (split16.hpp)
-    long long* dbg;                // S3_DBG builds (tools/s3_abl.sh probe): per wave of workgroup 0: [0] cycles in compute, [1] cycles waiting at the barrier, [2] steps
 };
 hipError_t stream3_launch(const Stream3Args& a, int grid, hipStream_t stream);
 

@@ -1031,14 +1031,14 @@ int pack_feat3_stream(dcscn_ctx* h, Op& op) {
     };
     int waves = 0;
     std::vector<int> cost;                          // MFMAs per row of each wave
-    a.role_conv[waves] = -1; a.role_tile[waves] = 0; cost.push_back(0); ++waves;
+    a.role_conv[waves] = -1; cost.push_back(0); ++waves;
     int pair_cost[2] = {0, 0};
     for (int i = 1; i < L; ++i) {
         const int mf = pack_conv(i - 1, op.fused[i], h->sched[i - 1], h->sched[i], ring[i - 1], ring[i], 2 * i);
         if (nin_on && i >= L - 2) { pair_cost[0] += mf; continue; }             // conv[L - 3], conv[L - 2] share a wave
         if (nin_on && i == L - 3) { pair_cost[1] += mf; continue; }             // conv[L - 4] shares one with B2
         if (waves >= kS3MaxWaves) return fail(h, DCSCN_ERR_UNSUPPORTED, "internal: feat3_stream needs more than %d waves", kS3MaxWaves);
-        a.role_conv[waves] = (int8_t)(i - 1); a.role_tile[waves] = 0; cost.push_back(mf); ++waves;
+        a.role_conv[waves] = (int8_t)(i - 1); cost.push_back(mf); ++waves;
     }
     if (nin_on) {
         const dcscn_config& c = h->cfg;
@@ -1099,8 +1099,8 @@ int pack_feat3_stream(dcscn_ctx* h, Op& op) {
         for (int i = 0; i < waves; ++i) order[i] = i;
         std::sort(order.begin(), order.end(), [&](int x, int y) { return cost[x] > cost[y]; });
         int load[4] = {0, 0, 0, 0}, used[4] = {0, 0, 0, 0};
-        int8_t rc[kS3MaxWaves], rt[kS3MaxWaves];
-        for (int w = 0; w < kS3MaxWaves; ++w) { rc[w] = -1; rt[w] = 0; }
+        int8_t rc[kS3MaxWaves];
+        for (int w = 0; w < kS3MaxWaves; ++w) rc[w] = -1;
         for (int idx : order) {
             int pick = -1;
             for (int sd = 0; sd < 4; ++sd) {
@@ -1108,11 +1108,11 @@ int pack_feat3_stream(dcscn_ctx* h, Op& op) {
                 if (used[sd] < cap && (pick < 0 || load[sd] < load[pick])) pick = sd;
             }
             const int w = pick + 4 * used[pick];
-            rc[w] = a.role_conv[idx]; rt[w] = a.role_tile[idx];
+            rc[w] = a.role_conv[idx];
             used[pick] += 1;
             load[pick] += cost[idx] + 20;
         }
-        for (int w = 0; w < kS3MaxWaves; ++w) { a.role_conv[w] = rc[w]; a.role_tile[w] = rt[w]; }
+        for (int w = 0; w < kS3MaxWaves; ++w) a.role_conv[w] = rc[w];
     }
     const int rc = upload(h, blob.data(), blob.size() * sizeof(float), (void**)&op.d_w);
     op.h16.on = rc == DCSCN_OK;

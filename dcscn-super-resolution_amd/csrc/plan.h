@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -183,6 +182,7 @@ struct dcscn_ctx {
     unsigned long long* d_digest = nullptr;   // debug_digest: one arena checksum per op of the last pass + one of y (dcscn_debug_digests)
     int debug_digest = 0;
     bool conv3_h8 = true;                    // two-group 3x3 layers on conv3_h8 (option "conv3_h8"); off: conv3_h everywhere
+    bool nin_h8 = true;                      // the widest NIN GEMMs on 256-pixel workgroups (option "nin_h8"); off: 128 pixels everywhere
     int n_cus = 256;                         // compute units of the device (persistent launches)
     int debug_poison = 0;                    // debug: LDS (bit 0) / VGPRs (bit 1) of every CU are filled with NaN patterns in front of every launch
     // option "graph_replay": a forward whose arguments repeat (same pointers, shape, stream) is captured into a hipGraph the second
@@ -191,11 +191,11 @@ struct dcscn_ctx {
     struct GraphKey {
         const void *x = nullptr, *x2 = nullptr, *y = nullptr;
         void* stream = nullptr;
-        int n = 0, H = 0, W = 0, split16 = 0, nb = 0, h8 = 0, p16 = 0;
+        int n = 0, H = 0, W = 0, split16 = 0, nb = 0, h8 = 0, nin_h8 = 0, p16 = 0;
         unsigned long long carve = 0;
         bool operator==(const GraphKey& o) const {
             return x == o.x && x2 == o.x2 && y == o.y && stream == o.stream && n == o.n && H == o.H && W == o.W && split16 == o.split16 && nb == o.nb &&
-                   h8 == o.h8 && p16 == o.p16 && carve == o.carve;
+                   h8 == o.h8 && nin_h8 == o.nin_h8 && p16 == o.p16 && carve == o.carve;
         }
     };
     GraphKey graph_seen, graph_key;          // the previous forward's arguments; the arguments graph_exec was captured with

@@ -51,7 +51,7 @@ __device__ __forceinline__ void tail_load_role(const TailArgs& a, const StreamAr
             const int it = lane + 64 * i;
             const int px = it / a.in.quads, quad = it - px * a.in.quads;
             const int cx = ri.sx + px;
-            dst[i] = live && it < n_items && cx >= 0 && cx < a.W && STREAM_ABL != 10 && STREAM_ABL != 13 && STREAM_ABL != 14 ? *reinterpret_cast<const f32x4*>(row + (size_t)cx * a.c2_stride + 4 * quad) : kStreamZero;
+            dst[i] = live && it < n_items && cx >= 0 && cx < a.W ? *reinterpret_cast<const f32x4*>(row + (size_t)cx * a.c2_stride + 4 * quad) : kStreamZero;
         }
     };
     load_row(0, now);
@@ -90,7 +90,7 @@ __device__ __forceinline__ void tail_up1_role(const TailArgs& a, const StreamArg
         f32x4 acc[1][8];
         bool keep = false;                  // false: zero row or a column outside the image -> zeros
         bool inside = false;                // wave uniform: the whole strip lies inside the image (no per-lane select needed)
-        if (live && STREAM_ABL != 11 && STREAM_ABL != 13 && STREAM_ABL != 14) {
+        if (live) {
             const StreamRow ri = stream_row(geo, j0, cur, g);
             if (!ri.zero) {
                 unsigned rowb[3];
@@ -141,7 +141,7 @@ __device__ __forceinline__ void tail_up2_role(const TailArgs& a, const StreamArg
         f32x4 acc[kStreamMT][1];
         bool okm[kStreamMT] = {false, false, false};
         bool inside = false;                // wave uniform: the strip lies inside the image
-        if (live && STREAM_ABL != 12 && STREAM_ABL != 13 && STREAM_ABL != 14) {
+        if (live) {
             const StreamRow ri = stream_row(geo, j0, cur, g);
             if (!ri.zero) {
                 const int ur = 2 * g + r2;
@@ -202,7 +202,7 @@ __device__ __forceinline__ void tail_rec_role(const TailArgs& a, const StreamArg
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int cx = cx0 + k;
-                const bool ok = in && ri.store && cx >= 4 * ri.ux0 && cx < 4 * ri.ux1 && STREAM_ABL != 9 && STREAM_ABL != 13;
+                const bool ok = in && ri.store && cx >= 4 * ri.ux0 && cx < 4 * ri.ux1;
                 dst[e][k] = ok ? a.x2[((size_t)ri.img * 4 * a.H + 4 * ri.r + 2 * c + e) * W4 + cx] : 0.0f;
             }
     };
@@ -213,7 +213,7 @@ __device__ __forceinline__ void tail_rec_role(const TailArgs& a, const StreamArg
         fetch(g + 1, nres);
         if (live) {
             const StreamRow ri = stream_row(geo, j0, cur, g);
-            if (ri.store && STREAM_ABL != 9 && STREAM_ABL != 13 && (!GATE || a.redo[1 + ri.img] != 0)) {
+            if (ri.store && (!GATE || a.redo[1 + ri.img] != 0)) {
                 const int vr0 = 4 * g + 2 * c;                  // first output row in V-row numbering
                 const int cx0 = 4 * ri.sx + 3 * lane;           // first of the lane's three HR columns
                 float v[4][5];

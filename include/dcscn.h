@@ -215,6 +215,9 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * "conv3_h8" (default 1; any time): 3x3 layers whose output channels form two channel groups (7 .. 12 tiles of 16) run on
  * conv3_h8 -- one persistent 8-wave workgroup per CU that stages a pixel tile's input once for both groups -- instead of two
  * conv3_h workgroups per tile; same filter image, bit-identical results.
+ * "nin_h8" (default 1; any time): the split16 1x1 GEMMs with K >= 1024 input channels, P16 sources and six full output tiles
+ * (A1 || B1 of the L12 nets) run on 256-pixel workgroups of conv_nin_h -- half the filter traffic per pixel -- instead of 128-pixel
+ * ones; same filter image, same products in the same order, bit-identical results.  0 = 128-pixel workgroups everywhere.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The

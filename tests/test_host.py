@@ -433,6 +433,26 @@ def test_library_has_no_packed_f32_instructions(tmp_path):
     assert packed == 0, "%d packed-f32 VALU instructions in libdcscn_hip.so" % packed
 
 
+def test_library_sources_hold_no_build_or_environment_switches():
+    """csrc/ holds only shipped code: no source reads the environment, and none has a build-overridable default
+    (`#ifndef NAME` directly followed by `#define NAME <value>`) -- the switches of the retired timing-only ablation and probe builds.
+    Include guards (`#define NAME` without a value) and #pragma once are not affected."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = [d for d in os.listdir(root) if d.endswith("_amd") and os.path.isdir(os.path.join(root, d))][0]
+    csrc = os.path.join(root, pkg, "csrc")
+    bad = []
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        if re.search(r"\bgetenv\b", text):
+            bad.append("%s: getenv" % name)
+        for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[ \t]*(?://.*)?\n[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\S", text, re.M):
+            if m.group(1) == m.group(2):
+                bad.append("%s: build-overridable default %s" % (name, m.group(1)))
+    assert len(os.listdir(csrc)) >= 20
+    assert not bad, bad
+
+
 def test_every_option_of_the_library_is_documented():
     """Each key dcscn_set_option accepts (csrc/api.hip) is described in include/dcscn.h and listed in INTEGRATION.md."""
     import re

@@ -3,9 +3,6 @@
 #ifndef C3H_MAX_NT
 #define C3H_MAX_NT 6
 #endif
-#ifndef C3H_ABL
-#define C3H_ABL 0
-#endif
 
 struct Layer3 { const char* name; int cin, cout, ps; };
 
@@ -75,56 +72,6 @@ static dim3 tiles_grid(ConvArgs& a, int n_groups) {
 struct R3 { double e32, e16, maxv; float ms32, ms16, mshp, msh8; int bad; };
 static int g_h8_wgs = 256;        // persistent workgroups of conv3_h8 (env C3E_WGS)
 static int g_hp_wgs = 512;        // persistent workgroups of conv3_hp (argv: conv3 <mode> ... or env C3P_WGS)
-static bool g_probe = false;      // ABL 7 / 8 builds: one more launch with the shader-clock probes on, summary printed
-
-// summary of the per-wave probe records of one launch (conv3_h.hpp, ABL 7 / 8)
-static void probe_report(const std::vector<long long>& pr, int n_wg, int n_taps, const char* name) {
-    struct W { long long t0, t1, t2, t3, sum, cb; unsigned hw, xcc; int wg, wave; };
-    std::vector<W> ws;
-    for (int g = 0; g < n_wg; ++g)
-        for (int w = 0; w < 4; ++w) {
-            const long long* r = &pr[((size_t)g * 4 + w) * 8];
-            if (r[3]) ws.push_back(W{r[0], r[1], r[2], r[3], r[4], r[5], (unsigned)r[6], (unsigned)r[7], g, w});
-        }
-    if (ws.empty()) { printf("  probe %s: no records\n", name); return; }
-    double pro = 0, loop = 0, epi = 0, sum = 0, cb = 0, dur = 0;
-    long long tmin = ws[0].t0, tmax = ws[0].t3;
-    for (auto& w : ws) {
-        pro += w.t1 - w.t0; loop += w.t2 - w.t1; epi += w.t3 - w.t2; sum += w.sum; cb += w.cb; dur += w.t3 - w.t0;
-        tmin = std::min(tmin, w.t0); tmax = std::max(tmax, w.t3);
-    }
-    const double n = (double)ws.size();
-    printf("  probe %s (ABL %d): %zu waves, kernel span %.0f cyc; per wave: total %.0f = prologue %.0f + K loop %.0f + epilogue %.0f; per tap %.0f (x%d);  "
-           "%s per tap %.0f;  chunk boundary (barrier + image write) %.0f in total\n",
-           name, C3H_ABL, ws.size(), (double)(tmax - tmin), dur / n, pro / n, loop / n, epi / n, loop / n / n_taps, n_taps,
-           C3H_ABL == 7 ? "wait + barrier" : "DMA / load issue", sum / n / n_taps, cb / n);
-    // co-residency: wave 0 records grouped by CU (xcc, se, sh, cu of HW_ID); start offset of each workgroup against the one that was already there
-    std::map<unsigned, std::vector<const W*>> cus;
-    for (auto& w : ws) if (w.wave == 0) cus[(w.xcc << 16) | ((w.hw >> 8) & 0xff)].push_back(&w);
-    std::vector<double> offs;
-    double alone = 0, both = 0;
-    for (auto& kv : cus) {
-        auto v = kv.second;
-        std::sort(v.begin(), v.end(), [](const W* a, const W* b) { return a->t0 < b->t0; });
-        for (size_t i = 1; i < v.size(); ++i) {
-            // the workgroup resident when v[i] starts: the latest-started earlier one that is still running
-            for (size_t j = i; j-- > 0;)
-                if (v[j]->t3 > v[i]->t0) { offs.push_back((double)(v[i]->t0 - v[j]->t0) / (double)(v[j]->t3 - v[j]->t0)); break; }
-        }
-        // time with one / two workgroups resident
-        std::vector<std::pair<long long, int>> ev;
-        for (auto* w : v) { ev.push_back({w->t0, 1}); ev.push_back({w->t3, -1}); }
-        std::sort(ev.begin(), ev.end());
-        int c = 0; long long last = 0;
-        for (auto& e : ev) { if (c == 1) alone += e.first - last; else if (c >= 2) both += e.first - last; c += e.second; last = e.first; }
-    }
-    int hist[10] = {0};
-    for (double o : offs) hist[std::min(9, std::max(0, (int)(o * 10)))]++;
-    printf("    %zu CUs seen; resident time with 2 workgroups %.1f %%, with 1 %.1f %%; start offset of a workgroup into its neighbour's life (tenths):", cus.size(),
-           100.0 * both / (both + alone), 100.0 * alone / (both + alone));
-    for (int i = 0; i < 10; ++i) printf(" %d", hist[i]);
-    printf("\n");
-}
 static int g_det_runs = 0;        // > 0: after the timing, run conv3_h this many more times and compare every output bit with the first run
 
 __global__ void count_diff(const float* a, const float* b, size_t n, unsigned long long* cnt, float* maxd) {
@@ -227,7 +174,7 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
     const dim3 grid = tiles_grid(b, ng);
     auto run16 = [&](auto nt_c) {
         constexpr int NTc = decltype(nt_c)::value;
-        auto k = conv3_h<NTc, 2, C3H_ABL>;
+        auto k = conv3_h<NTc>;
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NTc>::LDS_BYTES));
         return time_kernel(k, grid, C3HGeom<NTc>::LDS_BYTES, b, reps);
     };
@@ -265,37 +212,32 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
         const bool h8_ok = ng == 1 || (ng == 2) || (ng % 2 == 0 && nfull == ng);
         const long long n_units = n_tiles * ((ng + 1) / 2);
         const dim3 g8((unsigned)std::min<long long>(n_units, g_h8_wgs));
-        auto launch8 = [&](const void* probe) {
-            ConvArgs c = b8;
-            c.srctab = probe;
-            auto go = [&](auto c0_c, auto c1_c, auto dbg_c) {
+        auto launch8 = [&]() {
+            const ConvArgs c = b8;
+            auto go = [&](auto c0_c, auto c1_c) {
                 constexpr int C0 = decltype(c0_c)::value, C1c = decltype(c1_c)::value;
-                auto k = conv3_h8<C0, C1c, decltype(dbg_c)::value, (C0 >= 4 ? C0 : 0)>;       // two groups: nt = C0 >= 4 in the image; one group split: run time
+                auto k = conv3_h8<C0, C1c, (C0 >= 4 ? C0 : 0)>;       // two groups: nt = C0 >= 4 in the image; one group split: run time
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<C0>::LDS_BYTES));
                 hipLaunchKernelGGL(k, g8, dim3(512), C3EGeom<C0>::LDS_BYTES, 0, c);
             };
-            auto go_nt = [&](auto dbg_c) {
-#define H8_CASE(A, B) if (c0 == A && c1 == B) { go(std::integral_constant<int, A>{}, std::integral_constant<int, B>{}, dbg_c); return; }
+            auto go_nt = [&]() {
+#define H8_CASE(A, B) if (c0 == A && c1 == B) { go(std::integral_constant<int, A>{}, std::integral_constant<int, B>{}); return; }
                 H8_CASE(6, 6) H8_CASE(6, 5) H8_CASE(5, 5) H8_CASE(5, 4) H8_CASE(4, 4) H8_CASE(4, 3)
                 H8_CASE(3, 3) H8_CASE(3, 2) H8_CASE(2, 2) H8_CASE(2, 1) H8_CASE(1, 1) H8_CASE(1, 0)
 #undef H8_CASE
                 printf("no conv3_h8<%d, %d>\n", c0, c1); exit(1);
             };
             if (!h8_ok) return;
-#ifdef C3E_PROBE
-            if (probe) go_nt(std::integral_constant<int, 1>{}); else go_nt(std::integral_constant<int, 0>{});
-#else
-            go_nt(std::integral_constant<int, 0>{});
-#endif
+            go_nt();
         };
         hipEvent_t e0, e1;
         CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-        for (int i = 0; i < (timing ? 2 : 0); ++i) launch8(nullptr);
+        for (int i = 0; i < (timing ? 2 : 0); ++i) launch8();
         CK(hipDeviceSynchronize());
         float best = 1e30f;
         for (int i = 0; i < reps; ++i) {
             CK(hipEventRecord(e0, 0));
-            launch8(nullptr);
+            launch8();
             CK(hipEventRecord(e1, 0));
             CK(hipEventSynchronize(e1));
             float ms;
@@ -311,52 +253,10 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
         CK(hipFree(d_cnt)); CK(hipFree(d_max));
         if (!h8_ok) h8_diff = 0;
         if (h8_diff) ++r.bad;
-#ifdef C3E_PROBE
-        if (g_probe) {
-            long long* d_pr;
-            const size_t cnt = (size_t)g8.x * 8 * 8;
-            CK(hipMalloc(&d_pr, cnt * 8)); CK(hipMemset(d_pr, 0, cnt * 8));
-            launch8(d_pr);
-            CK(hipDeviceSynchronize());
-            std::vector<long long> pr(cnt);
-            CK(hipMemcpy(pr.data(), d_pr, cnt * 8, hipMemcpyDeviceToHost));
-            for (int hf = 0; hf < 2; ++hf) {
-                double life = 0, items = 0, ld = 0, cp = 0, bl = 0, bc = 0, ep = 0; int nw = 0;
-                for (size_t i = 0; i < cnt / 8; ++i) {
-                    const long long* q = &pr[i * 8];
-                    if (!q[1] || (int)((i % 8) / 4) != hf) continue;
-                    life += q[1] - q[0]; items += q[2]; ld += q[3]; cp += q[4]; bl += q[5]; bc += q[6]; ep += q[7]; ++nw;
-                }
-                const int n_taps = (tail_octs ? (n_chunks - 1) * 9 + c3h_tail_steps(tail_octs) : n_chunks * 9);
-                printf("  probe h8 %s half %d: %d waves, per item %.0f cycles; per tap: load phase %.0f + barrier wait %.0f, compute phase %.0f + barrier wait %.0f; epilogue %.0f per item\n",
-                       L.name, hf, nw, life / items, ld / items / n_taps, bl / items / n_taps, cp / items / n_taps, bc / items / n_taps, ep / items);
-            }
-            CK(hipFree(d_pr));
-        }
-#endif
         CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
         CK(hipFree(d_o8));
     }
 #endif
-    if (g_probe && (C3H_ABL == 7 || C3H_ABL == 8)) {
-        long long* d_pr;
-        const size_t cnt = (size_t)grid.x * 4 * 8;
-        CK(hipMalloc(&d_pr, cnt * 8)); CK(hipMemset(d_pr, 0, cnt * 8));
-        ConvArgs bp2 = b;
-        bp2.srctab = d_pr;
-        switch (nt) {
-            case 2: { auto k = conv3_h<2, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<2>::LDS_BYTES, 0, bp2); break; }
-            case 3: { auto k = conv3_h<3, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<3>::LDS_BYTES, 0, bp2); break; }
-            case 4: { auto k = conv3_h<4, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<4>::LDS_BYTES, 0, bp2); break; }
-            case 5: { auto k = conv3_h<5, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<5>::LDS_BYTES, 0, bp2); break; }
-            default: { auto k = conv3_h<6, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<6>::LDS_BYTES, 0, bp2); break; }
-        }
-        CK(hipDeviceSynchronize());
-        std::vector<long long> pr(cnt);
-        CK(hipMemcpy(pr.data(), d_pr, cnt * 8, hipMemcpyDeviceToHost));
-        probe_report(pr, (int)grid.x, (tail_octs ? n_chunks - 1 : n_chunks) * 9, L.name);
-        CK(hipFree(d_pr));
-    }
     if (g_det_runs > 0) {
         float* d_first;
         unsigned long long* d_cnt; float* d_max;
@@ -370,10 +270,10 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
                 hipLaunchKernelGGL(fill_act, dim3(4096), dim3(256), 0, 0, d_in, in_floats, 99u + L.cin);
             }
             switch (nt) {
-                case 1: { auto k = conv3_h<1, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<1>::LDS_BYTES, 0, b); break; }
-                case 2: { auto k = conv3_h<2, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<2>::LDS_BYTES, 0, b); break; }
-                case 3: { auto k = conv3_h<3, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<3>::LDS_BYTES, 0, b); break; }
-                default: { auto k = conv3_h<4, 2, C3H_ABL>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<4>::LDS_BYTES, 0, b); break; }
+                case 1: { auto k = conv3_h<1>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<1>::LDS_BYTES, 0, b); break; }
+                case 2: { auto k = conv3_h<2>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<2>::LDS_BYTES, 0, b); break; }
+                case 3: { auto k = conv3_h<3>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<3>::LDS_BYTES, 0, b); break; }
+                default: { auto k = conv3_h<4>; hipLaunchKernelGGL(k, grid, dim3(256), C3HGeom<4>::LDS_BYTES, 0, b); break; }
             }
             hipLaunchKernelGGL(count_diff, dim3(2048), dim3(256), 0, 0, d_first, d_o16, out_floats, d_cnt, d_max);
             unsigned long long c; float m;
@@ -413,7 +313,7 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
             s32 += a32e * a32e; s16 += a16e * a16e; ++nn;
             r.maxv = std::fmax(r.maxv, std::fabs((double)rf[i]));
         }
-    const bool ok = (C3H_ABL != 0) || (r.e16 <= 2.0 * r.e32 + 2e-6 * r.maxv && r.e16 <= 1e-5 * r.maxv && std::isfinite(r.e16) && stray == 0.0);
+    const bool ok = r.e16 <= 2.0 * r.e32 + 2e-6 * r.maxv && r.e16 <= 1e-5 * r.maxv && std::isfinite(r.e16) && stray == 0.0;
     r.bad += !ok;
     const double flop = 2.0 * 9 * L.cin * (double)L.cout * N * H * W;
     if (h8_diff) printf("  ** conv3_h8 differs from conv3_h in %llu elements\n", h8_diff);
@@ -464,18 +364,6 @@ static int conv3_main(int argc, char** argv) {
         const int N = argc > 4 ? atoi(argv[4]) : 96;
         const Layer3 layers[] = {{"CNN2", 196, 166, 1}, {"CNN5", 133, 120, 1}, {"CNN9", 86, 76, 1}, {"CNN12", 57, 48, 1}, {"B2", 32, 32, 1}};
         for (const Layer3& L : layers) run_conv3(L, N, 48, 48, 1, false, 0, false);
-        return 0;
-    }
-    if (!strcmp(what, "probe")) {
-        g_probe = true;
-        const Layer3 layers[] = {{"CNN2", 196, 166, 1}, {"CNN5", 133, 120, 1}, {"CNN9", 86, 76, 1}, {"CNN12", 57, 48, 1}};
-        for (const Layer3& L : layers) run_conv3(L, 1024, 48, 48, 1, true, 0, false);
-        return 0;
-    }
-    if (!strcmp(what, "abl")) {
-        printf("ABL %d\n", C3H_ABL);
-        const Layer3 layers[] = {{"CNN2", 196, 166, 1}, {"CNN5", 133, 120, 1}, {"CNN9", 86, 76, 1}, {"CNN12", 57, 48, 1}};
-        for (const Layer3& L : layers) run_conv3(L, 1024, 48, 48, 1, true, 0, false);
         return 0;
     }
     if (!strcmp(what, "bench") || !strcmp(what, "all")) {

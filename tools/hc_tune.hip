@@ -161,7 +161,7 @@ static R run_conv3(const Layer3& L, int N, int H, int W, bool timing, int overfl
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
                 hipLaunchKernelGGL(k, g8, dim3(512), lds, 0, b);
             } else {
-                auto k = conv3_h<NT, 2, 0, true>;
+                auto k = conv3_h<NT, 2, true>;
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NT>::LDS_BYTES));
                 const long long ids = ((n_tiles + 7) / 8) * 8;
                 hipLaunchKernelGGL(k, dim3((unsigned)ids), dim3(256), C3HGeom<NT>::LDS_BYTES, 0, base);

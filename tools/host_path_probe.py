@@ -1,4 +1,4 @@
-"""Where the host-buffer entry point spends its time (DCSCN_TRACE_HOST=1 makes the library print its own split)."""
+"""Where the host-buffer entry point spends its time, timed from Python."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

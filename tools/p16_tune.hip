@@ -151,14 +151,14 @@ static R run_conv3(const Layer3& L, int N, int H, int W, bool timing, int overfl
         auto go = [&](auto c0_c, auto c1_c) {
             constexpr int C0 = decltype(c0_c)::value, C1c = decltype(c1_c)::value;
             if (p16v) {
-                auto k = conv3_h8<C0, C1c, 0, (C0 >= 4 ? C0 : 0), true>;
+                auto k = conv3_h8<C0, C1c, (C0 >= 4 ? C0 : 0), true>;
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<C0>::LDS_BYTES));
                 hipLaunchKernelGGL(k, g8, dim3(512), C3EGeom<C0>::LDS_BYTES, 0, b);
             } else {
 #ifdef P16_TUNE_WIDE_ONLY
                 return;
 #endif
-                auto k = conv3_h8<C0, C1c, 0, (C0 >= 4 ? C0 : 0), false>;
+                auto k = conv3_h8<C0, C1c, (C0 >= 4 ? C0 : 0), false>;
                 CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<C0>::LDS_BYTES));
                 hipLaunchKernelGGL(k, g8, dim3(512), C3EGeom<C0>::LDS_BYTES, 0, a);
             }

@@ -20,9 +20,6 @@ using namespace dcscn;
 #ifndef W2_PF
 #define W2_PF 3
 #endif
-#ifndef W2_ABL
-#define W2_ABL 0
-#endif
 
 #define CK(x)                                                                              \
     do {                                                                                   \
@@ -218,11 +215,11 @@ static Result run(const Layer& L, int N, int H, int W, int n_check, bool time_ol
         b.out0 = OutDesc{g_out, L.out_stride, L.out_off, owidth};
         b.out1 = b.out0;
         const dim3 grid = wino_grid(b, ng);
-        auto kern = conv_wino2<NT, W2_WPS, W2_PF, W2_ABL>;
+        auto kern = conv_wino2<NT, W2_WPS, W2_PF>;
         const size_t lds = G2::LDS_BYTES;
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CK(hipMemset(g_out, 0, out_floats * sizeof(float)));
-        r.ms_new = time_kernel(kern, grid, lds, b, (time_old || W2_ABL || N > 64) ? 5 : 1);
+        r.ms_new = time_kernel(kern, grid, lds, b, (time_old || N > 64) ? 5 : 1);
         const size_t cnt = (size_t)n_check * H * L.ps * W * L.ps * L.out_stride;
         std::vector<float> rf(cnt), o(cnt);
         CK(hipMemcpy(rf.data(), g_ref, cnt * sizeof(float), hipMemcpyDeviceToHost));
@@ -276,14 +273,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(g_bias, b.data(), 4096 * sizeof(float), hipMemcpyHostToDevice));
         CK(hipMemcpy(g_alpha, al.data(), 4096 * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (!strcmp(mode, "abl")) {            // a few layers only (ablated builds give wrong results by design)
-        const Layer layers[] = {{"CNN2", 196, 166, 1316, 0, 1316, 196, 1}, {"CNN3", 166, 148, 1316, 196, 1316, 364, 1}, {"CNN4", 148, 133, 1316, 364, 1316, 512, 1},
-                                {"CNN7", 108, 97, 1316, 768, 1316, 876, 1}, {"CNN3t", 166, 16, 1316, 196, 1316, 364, 1}};
-        printf("ABL %d PF %d\n", W2_ABL, W2_PF);
-        for (const Layer& L : layers) {
-            run_layer(L, N, H, W, 1, false);
-        }
-    } else if (!strcmp(mode, "bench")) {
+    if (!strcmp(mode, "bench")) {
         // the 3x3 layers of L12_F196to48 x2 as the plan lays them out (concat stride 1316, slices at 4-channel boundaries)
         const Layer layers[] = {
             {"CNN2", 196, 166, 1316, 0, 1316, 196, 1},   {"CNN3", 166, 148, 1316, 196, 1316, 364, 1},  {"CNN4", 148, 133, 1316, 364, 1316, 512, 1},
