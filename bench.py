@@ -12,24 +12,31 @@ rank (512 / 256 / 128 per GPU at 2 / 4 / 8).  Independent patches 
 no data-path collective.  A step is one forward pass of the rank's whole batch with x / x2 already
 resident in HBM and y left in HBM.  Weights are seeded synthetic (the trained L12 blobs are not shipped).
 The graph executed is the library default (linear tail folded into one 5x5 conv, include/dcscn.h
-"fold_linear_tail"); the layer-by-layer graph is timed beside it at N = 1 (``layer_by_layer``).
+"fold_linear_tail").
 
 Arithmetic: the library default ("split16", include/dcscn.h) runs the 3x3 stack and the wide 1x1 convs on the f16 matrix
 pipe at f32 accuracy -- every f32 operand as an f16 (hi, lo) pair, three products per MAC, f32 accumulation (measured error
-below the f32 kernels', profiles/r03_f16x3_numerics.txt); everything else is f32.  The pure-f32 kernels (split16 = 0) are
-timed in the same line (`f32_path`).  With N > 1 the line also carries the strong-scaling leg of BASELINE configs[2]
-(`strong_scaling`: 1024 patches in total, 1024 / N per rank).
+below the f32 kernels', profiles/r03_f16x3_numerics.txt); everything else is f32.
 
-Rank 0 prints one JSON line: LR Mpixels/s over all GPUs, plus
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Rank 0 prints one JSON line:
+LR Mpixels/s over all GPUs, plus
   roofline      -- the dominant kernel (the 3x3 convs: conv3_h on v_mfma_f32_16x16x32_f16, or conv_wino2 on f32 MFMA with
                    split16 = 0): `achieved` = the FLOPs the kernel really issues per step / its summed launch time, measured
                    with HIP events on the launch stream inside the timed steps; `frac` = achieved / dense MFMA peak of the
                    instruction's dtype = matrix-pipe utilisation (<= 1); `useful_frac` leaves out channel padding.  The
                    direct-form (algorithmic, f32-equivalent) FLOP rate of the same launches is reported against the f32 peak
-                   (`vs_f32_peak`).  `traffic` and `sustained_clock_GHz` are REPLAYED from the committed rocprofv3 PMC passes of
-                   this command (profiles/r*_pmc_per_dispatch.json): PMC counters cannot be read in-process.
+                   (`vs_f32_peak`).
+
+``--full`` adds everything else the benchmark measures, after the headline and without touching it:
+  north_star, roofline traffic -- REPLAYED from the committed rocprofv3 PMC passes of this command
+                   (profiles/r*_pmc_per_dispatch.json; `sustained_clock_GHz` among them): PMC counters cannot be read in-process.
   cpu_baseline  -- the float32 torch-CPU restatement of the same graph (oracle/cpu_path_torch.py;
                    TensorFlow is not installable) timed on the host cores on a bounded sample.
+  at N = 1: host_path (PCIe-inclusive host-buffer entry points), graph_replay, float32_tensors (p16 = 0), f32_path (the
+                   pure-f32 kernels, split16 = 0), layer_by_layer (fold_linear_tail = 0), other_configs (BASELINE C2 and C5)
+                   and parity (the shipped c-DCSCN checkpoint on Set5 against the committed float64 goldens).
+  at N > 1: strong_scaling, the strong-scaling leg of BASELINE configs[2] (1024 patches in total, 1024 / N per rank).
+The --no-* options below leave single legs out of a --full run.
 
 ``--dump-outputs DIR`` writes the y of the last timed step to DIR as .npy (inputs and weights are seeded: the same arguments
 give the same inputs), so that two builds can be compared output for output.
@@ -387,19 +394,23 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--patches", type=int, default=PATCHES_PER_GPU, help="48x48 patches per GPU")
     ap.add_argument("--sub-batch-pixels", type=int, default=0, help="override the engine's pass size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures (replayed PMC figures, CPU baseline, "
+                         "host path, graph replay, p16 = 0, f32 path, layer-by-layer graph, C2 / C5, Set5 parity; strong-scaling "
+                         "leg at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--ops", action="store_true", help="print the per-launch table to stderr")
     ap.add_argument("--no-winograd", action="store_true", help="keep the 3x3 convs on the direct implicit-GEMM kernel")
     ap.add_argument("--cpu-sample", type=int, default=64, help="patches in the CPU baseline sample")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive timing of the host-buffer entry points")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip the PCIe-inclusive timing of the host-buffer entry points")
     ap.add_argument("--no-opt-in", "--no-layer-by-layer", dest="no_extra_graph", action="store_true",
-                    help="skip the extra timing of the layer-by-layer graph")
+                    help="--full: skip the graph-replay, p16 = 0, f32 and layer-by-layer legs, C2 / C5 and the Set5 parity leg")
     ap.add_argument("--layer-by-layer", action="store_true",
                     help="headline on the reference's layers one by one (fold_linear_tail = 0) instead of the library default")
     ap.add_argument("--no-split16", action="store_true", help="headline on the pure f32 kernels (split16 = 0: conv_wino2 / conv_nin)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C2 / C5 legs (other_configs) and the Set5 parity leg")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the C2 / C5 legs (other_configs) and the Set5 parity leg")
     ap.add_argument("--other-steps", type=int, default=20, help="timed steps of each other_configs leg")
-    ap.add_argument("--no-strong-leg", action="store_true", help="N > 1: skip the extra strong-scaling leg (1024 patches in total)")
+    ap.add_argument("--no-strong-leg", action="store_true", help="--full, N > 1: skip the extra strong-scaling leg (1024 patches in total)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --patches is the GLOBAL batch, split into contiguous shards over the ranks")
     ap.add_argument("--check-output", action="store_true",
@@ -555,10 +566,10 @@ def main():
             mine = [d for p in parts for d in p]       # rank order == patch order (contiguous shards)
         digest = hashlib.sha256("".join(mine).encode()).hexdigest()
     global_patches = args.patches if args.strong else n * world
-    # N > 1, weak headline: the strong-scaling leg of BASELINE configs[2] in the same line (one seeded global batch of
+    # --full, N > 1, weak headline: the strong-scaling leg of BASELINE configs[2] in the same line (one seeded global batch of
     # PATCHES_PER_GPU patches, contiguous shard per rank), timed exactly like the headline
     strong_leg = None
-    if world > 1 and not args.strong and not args.no_strong_leg:
+    if args.full and world > 1 and not args.strong and not args.no_strong_leg:
         from dcscn_amd import shard
         lo, hi = shard.shard_bounds(PATCHES_PER_GPU, rank, world)
         ns_ = hi - lo
@@ -629,7 +640,8 @@ def main():
                          fx / (ms * 1e-3) / 1e12 if ms else 0, by / (ms * 1e-3) / 1e9 if ms else 0), file=sys.stderr)
         nin_ms = sum(ms for o, ms in zip(ops, per_op_ms) if o["kernel"] in ("conv_igemm", "conv_nin", "conv_nin_h") and o["kernel_size"] == 1)
         full_workload = n == PATCHES_PER_GPU and not args.no_winograd
-        traffic, north_star = pmc_replay(dom_ms, nin_ms, dom_bytes, {o["kernel"] for o in ops}) if full_workload else (None, None)
+        traffic, north_star = (pmc_replay(dom_ms, nin_ms, dom_bytes, {o["kernel"] for o in ops}) if args.full and full_workload
+                               else (None, None))
         graph = ("linear tail (Up-PS conv + depth_to_space + R-CNN1) folded into one 5x5 conv -- library default, include/dcscn.h fold_linear_tail"
                  if folded else "the reference's layers, one launch per layer (B1+A1 share a launch)")
         result = {
@@ -700,7 +712,9 @@ def main():
             result["dump_outputs"] = dumped
         if north_star:
             result["north_star"] = north_star
-        if world == 1 and not args.no_cpu_baseline:
+        # --full: the legs beside the headline, each after the headline's timed steps and dump
+        legs = args.full and world == 1
+        if legs and not args.no_cpu_baseline:
             import cpu_path_torch as T
             cs = min(args.cpu_sample, n)
             xs = x[:cs].cpu().numpy()
@@ -720,7 +734,7 @@ def main():
                           "not installable), best of 2 after 1 warm-up per setting, %.2f s/forward" % (cs, n, layout, threads, sec),
                 "max_abs_diff_vs_hip": dev_err,
             }
-        if world == 1 and not args.no_host_path:
+        if legs and not args.no_host_path:
             # PCIe-inclusive rate of the host-buffer entry points (never `value`): numpy in, numpy out, synchronous
             try:
                 # numpy-owned copies: buffers handed out by torch's CPU allocator upload 20x slower through hipMemcpy
@@ -746,7 +760,7 @@ def main():
                 }
             except Exception as exc:
                 result["host_path"] = {"error": str(exc)}
-        if world == 1 and not args.no_extra_graph:
+        if legs and not args.no_extra_graph:
             # beside the headline: the same step replayed from a hipGraph (option graph_replay: captured on the second call with
             # the same arguments) -- one graph launch instead of the pass's kernel launches
             try:
@@ -769,7 +783,7 @@ def main():
                 eng.set_option("graph_replay", 0)
             except Exception as exc:
                 result["graph_replay"] = {"error": str(exc)}
-        if world == 1 and on_f16 and not args.no_extra_graph:
+        if legs and on_f16 and not args.no_extra_graph:
             # beside the headline: the same engine with float32 tensors between the split16 launches (p16 = 0: the r04 data path)
             try:
                 y_p16 = y.clone()
@@ -796,7 +810,7 @@ def main():
                 eng.synchronize()
             except Exception as exc:
                 result["float32_tensors"] = {"error": str(exc)}
-        if world == 1 and on_f16 and not args.no_extra_graph:
+        if legs and on_f16 and not args.no_extra_graph:
             # beside the headline: the same engine on the pure f32 kernels (split16 = 0), same inputs, timed the same way
             try:
                 y_h16 = y.clone()
@@ -820,7 +834,7 @@ def main():
                 eng.synchronize()
             except Exception as exc:
                 result["f32_path"] = {"error": str(exc)}
-        if world == 1 and folded and not args.no_extra_graph:
+        if legs and folded and not args.no_extra_graph:
             # beside the headline: the same inputs through the layer-by-layer graph (fold_linear_tail = 0), timed the same way
             try:
                 y_ref = y.clone()
@@ -845,7 +859,7 @@ def main():
                 eng2.close()
             except Exception as exc:      # the headline line must survive a failure of the extra leg
                 result["layer_by_layer"] = {"error": str(exc)}
-        if world == 1 and not args.no_other_configs and not args.no_extra_graph:
+        if legs and not args.no_other_configs and not args.no_extra_graph:
             # SURVEY.md 8(d) "also C2, C5": the other single-GPU BASELINE configurations, and the metric's "PSNR delta vs ref on Set5"
             result["other_configs"] = {}
             for key in OTHER_CONFIGS:

@@ -1,5 +1,6 @@
 """bench.py --dump-outputs: the output of the last timed step, written as .npy so that two builds can be compared output for
-output, and --steps as the number of timed steps in the result line."""
+output, and --steps as the number of timed steps in the result line.  A plain run prints the headline alone; --full adds every
+other leg."""
 import hashlib
 import json
 import os
@@ -46,6 +47,44 @@ def _bench(dump, steps):
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
     return json.loads(lines[0])
+
+
+# what only --full adds to the line (strong_scaling: N > 1 only)
+FULL_LEGS = ("north_star", "cpu_baseline", "host_path", "graph_replay", "float32_tensors", "f32_path", "layer_by_layer",
+             "other_configs", "parity")
+
+
+def _line(args):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args
+    out = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone():
+    r = _line(["--patches", "6", "--steps", "2", "--warmup", "1"])
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+    assert abs(r["value"] - 6 * 48 * 48 / (r["ms_per_step"] * 1e-3) / 1e6) / r["value"] < 1e-3
+    assert r["roofline"]["kernel_ms_per_step"] > 0 and r["dtype"]
+    assert not [k for k in FULL_LEGS if k in r]
+
+
+@pytest.mark.gpu
+def test_full_run_adds_every_leg():
+    """--full on a small batch (--cpu-sample 2, --other-steps 1): every leg is there and none failed."""
+    r = _line(["--patches", "6", "--steps", "1", "--warmup", "1", "--full", "--cpu-sample", "2", "--other-steps", "1"])
+    assert r["steps"] == 1 and r["ms_per_step"] > 0
+    # (north_star: the committed counters are replayed for the 1024-patch workload only)
+    for k in FULL_LEGS[1:]:
+        assert k in r and "error" not in r[k], (k, r.get(k))
+    for key in ("C2", "C5"):
+        assert "error" not in r["other_configs"][key] and r["other_configs"][key]["steps"] == 1
+    assert r["graph_replay"]["bit_identical_to_plain_launches"] and r["float32_tensors"]["bit_identical_to_headline"]
+    assert r["parity"]["set5_psnr_delta_db"] <= r["parity"]["bars"]["set5_psnr_delta_db"]
+    assert r["parity"]["max_abs"] <= r["parity"]["bars"]["max_abs"]
 
 
 @pytest.mark.gpu
