@@ -792,6 +792,7 @@ int dcscn_destroy(dcscn_handle h) {
     for (hipEvent_t e : h->host_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     train_free(h);
+    train_batches_free(h);
     for (void* p : h->device_allocs) (void)hipFree(p);
     for (void* p : h->pack_allocs) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);

@@ -58,6 +58,7 @@ struct ColSeg {
 };
 
 struct TrainState;   // train.hip
+struct TrainBatches; // train_data.hip
 
 struct Op {
     OpKind kind = OP_CONV;
@@ -153,8 +154,9 @@ struct dcscn_ctx {
     // host-path staging
     float* io_x = nullptr; float* io_x2 = nullptr; float* io_y = nullptr;
     size_t io_x_cap = 0, io_y_cap = 0;
-    // bicubic resize (resample.hip): Pillow coefficient tables per (in, out) size, and the intermediate image
-    struct ResampleTable { int ksize = 0; int* d_bounds = nullptr; double* d_kk = nullptr; };
+    // bicubic resize (resample.hip): Pillow coefficient tables per (in, out) size, and the intermediate image; d_k8 = the
+    // 8-bit fixed-point form of d_kk (train_data.hip, made on first use)
+    struct ResampleTable { int ksize = 0; int* d_bounds = nullptr; double* d_kk = nullptr; int* d_k8 = nullptr; };
     std::map<std::pair<int, int>, ResampleTable> resample_tables;
     float* rs_tmp = nullptr; size_t rs_tmp_cap = 0;
     // self-ensemble (ensemble.hip): flipped copies, their outputs, float64 mean (as 2 floats per double)
@@ -232,6 +234,7 @@ struct dcscn_ctx {
     std::vector<double> prof_ms;
     std::vector<void*> pack_allocs;          // device images finalize_op made (freed and rebuilt when training changed the variables)
     dcscn_impl::TrainState* train = nullptr;      // train.hip: the training plan, variables and slots (dcscn_train_begin)
+    dcscn_impl::TrainBatches* batches = nullptr;  // train_data.hip: device-resident training images and the batch planes
 };
 
 namespace dcscn_impl {
@@ -281,6 +284,11 @@ int repack_weights(dcscn_ctx* h);
 // train.hip
 void train_free(dcscn_ctx* h);
 int train_sync_inference(dcscn_ctx* h);
+// train_data.hip: validate n patches; build them into device buffers x [n, L, L], x2 and y_true [n, L s, L s] on `stream`
+int check_patches(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value);
+int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value, float* x, float* x2, float* y_true,
+                       hipStream_t stream);
+void train_batches_free(dcscn_ctx* h);
 // exec.hip
 int ensure_workspace(dcscn_ctx* h, int nb, int H, int W, hipStream_t stream);
 // redo = false: the launch of the pass (split16 kernels where the handle's options allow); true: the op's float32 launch gated by the

@@ -827,6 +827,25 @@ int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, con
     return DCSCN_OK;
 }
 
+int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr, uint64_t dropout_key,
+                             double* stats) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    TrainState* t = h->train;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = carve(h, t, n, lr_size, lr_size))) return rc;
+    hipStream_t st = h->stream;
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;   // train_data.hip
+    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st))) return rc;
+    if ((rc = apply_update(h, t, lr, st))) return rc;
+    if (stats) {
+        HIP_TRY(h, hipMemcpyAsync(stats, t->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    return DCSCN_OK;
+}
+
 // "<var>", "<var>/grad", "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power"
 static int train_tensor(dcscn_ctx* h, const char* name, float** dev, int64_t* count, bool* is_var) {
     TrainState* t = h->train;

@@ -1,0 +1,305 @@
+// Training batches on the device (helper/loader.py DynamicDataSets.load_batch_image, loader.py:278-355 of the reference):
+// per patch a crop of HR = L s pixels of an image kept on the device, its Y (RGB) or its pixels (grey), fliplr, then
+// LR = bicubic 1/s and x2 = bicubic s of LR as Pillow computes them -- mode "F" for the float Y of RGB images, mode "L" (8-bit
+// fixed point) for grey images -- and the max_value / float32 cast rules of load_batch_image + train_batch (include/dcscn.h).
+//
+// A batch is, on one stream and without a host synchronisation:
+//   batch_gather  (1 launch per 32 patches)  crop + Y / grey + fliplr into compact HR planes (float32 for RGB patches, uint8
+//                                            for grey ones, numbered in batch order per kind); writes y_true
+//   resize_device (4 launches, RGB patches)  resample.hip's mode-"F" kernels: HR -> LR -> x2
+//   resample_*8   (4 launches, grey patches) Pillow's 8-bpc kernels: HR -> LR -> x2 through uint8 intermediates
+//   batch_finish  (1 launch per 32 patches)  max_value and float32 cast of LR and x2 into x, x2
+// Everything here is a few hundred KB of elementwise work per batch; the kernels are the plain one-thread-per-pixel form.
+#include "plan.h"
+
+#pragma clang fp contract(off)
+
+namespace dcscn_impl {
+
+struct TrainImage {
+    uint8_t* px = nullptr;
+    int H = 0, W = 0, C = 0;
+};
+
+struct TrainBatches {
+    std::vector<TrainImage> images;
+    float* planes = nullptr; size_t planes_cap = 0;   // the HR / LR / x2 planes of one batch (capacity in floats)
+    float* out = nullptr; size_t out_cap = 0;         // dcscn_train_build_batch: x, x2, y_true before the copy to the host
+};
+
+namespace {
+
+constexpr int kChunk = 32;          // patches per gather / finish launch (their descriptors travel as kernel arguments)
+constexpr int kPrecisionBits = 22;  // Pillow Resample.c: PRECISION_BITS = 32 - 8 - 2
+
+struct PatchDesc {
+    const uint8_t* px;              // the image, [H, W, c] uint8
+    int32_t w, c, top, left, flip;
+    int32_t slot;                   // index among the batch's patches of the same kind (c == 3: float planes, c == 1: uint8 planes)
+};
+struct PatchChunk {
+    PatchDesc p[kChunk];
+};
+
+// convert_rgb_to_y: numpy's image.dot(M.T) + 16 in float64, the FMA chain of color.hip's dot3 (bit-identical to the host)
+__device__ __forceinline__ double luma(double r, double g, double b) {
+    return __fma_rn(b, 25.064 / 256.0, __fma_rn(g, 129.057 / 256.0, r * (65.738 / 256.0))) + 16.0;
+}
+
+// grid (ceil(HR^2 / 256), patches of the chunk); y_true is offset to the chunk's first patch
+__global__ __launch_bounds__(256) void batch_gather_kernel(PatchChunk pc, int hr, int mul, double scale, float* __restrict__ yf,
+                                                           uint8_t* __restrict__ y8, float* __restrict__ y_true) {
+    const long long hr2 = (long long)hr * hr;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= hr2) return;
+    const PatchDesc& d = pc.p[blockIdx.y];
+    const int i = (int)(idx / hr), j = (int)(idx % hr);
+    const size_t src = (size_t)(d.top + i) * d.w + d.left + (d.flip ? hr - 1 - j : j);
+    double v;
+    if (d.c == 1) {
+        const uint8_t u = d.px[src];
+        y8[(size_t)d.slot * hr2 + idx] = u;
+        v = (double)u;
+    } else {
+        const uint8_t* p = d.px + 3 * src;
+        v = luma((double)p[0], (double)p[1], (double)p[2]);
+        yf[(size_t)d.slot * hr2 + idx] = (float)v;          // Image.fromarray(float64): mode "F" holds float32(Y)
+    }
+    y_true[(size_t)blockIdx.y * hr2 + idx] = (float)(mul ? v * scale : v);
+}
+
+// Pillow ImagingResampleHorizontal_8bpc: out[row][xx] = clip8((1 << 21 + sum_i in[row][xmin + i] * k8[xx][i]) >> 22)
+__device__ __forceinline__ uint8_t clip8(int ss) {
+    const int v = ss >> kPrecisionBits;
+    return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+
+__global__ __launch_bounds__(256) void resample_h8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
+                                                          const int* __restrict__ kk, int ksize, long long rows, int w, int ow) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * ow) return;
+    const int xx = (int)(idx % ow);
+    const long long row = idx / ow;
+    const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
+    const uint8_t* p = in + row * w + xmin;
+    const int* k = kk + (size_t)xx * ksize;
+    int ss = 1 << (kPrecisionBits - 1);
+    for (int i = 0; i < n; ++i) ss += (int)p[i] * k[i];
+    out[idx] = clip8(ss);
+}
+
+// ImagingResampleVertical_8bpc
+__global__ __launch_bounds__(256) void resample_v8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
+                                                          const int* __restrict__ kk, int ksize, int n_img, int h, int oh, int w) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n_img * oh * w) return;
+    const int x = (int)(idx % w);
+    const long long t = idx / w;
+    const int yy = (int)(t % oh);
+    const long long img = t / oh;
+    const int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
+    const uint8_t* p = in + (img * h + ymin) * w + x;
+    const int* k = kk + (size_t)yy * ksize;
+    int ss = 1 << (kPrecisionBits - 1);
+    for (int i = 0; i < n; ++i) ss += (int)p[(size_t)i * w] * k[i];
+    out[idx] = clip8(ss);
+}
+
+// load_batch_image's max_value rule and train_batch's float32 cast: float32 planes (RGB) times float32(scale); uint8 planes
+// (grey) times scale in float64 (numpy: uint8 array * Python float -> float64)
+__device__ __forceinline__ float cast_rgb(float v, int mul, double scale) { return mul ? v * (float)scale : v; }
+__device__ __forceinline__ float cast_grey(uint8_t u, int mul, double scale) { return mul ? (float)((double)u * scale) : (float)u; }
+
+// grid (ceil(HR^2 / 256), patches of the chunk); x, x2 offset to the chunk's first patch
+__global__ __launch_bounds__(256) void batch_finish_kernel(PatchChunk pc, int lr, int hr, int mul, double scale, const float* __restrict__ f_lr,
+                                                           const float* __restrict__ f_x2, const uint8_t* __restrict__ g_lr,
+                                                           const uint8_t* __restrict__ g_x2, float* __restrict__ x, float* __restrict__ x2) {
+    const long long hr2 = (long long)hr * hr, lr2 = (long long)lr * lr;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= hr2) return;
+    const PatchDesc& d = pc.p[blockIdx.y];
+    const size_t s_hr = (size_t)d.slot * hr2 + idx, s_lr = (size_t)d.slot * lr2 + idx;
+    x2[(size_t)blockIdx.y * hr2 + idx] = d.c == 1 ? cast_grey(g_x2[s_hr], mul, scale) : cast_rgb(f_x2[s_hr], mul, scale);
+    if (idx < lr2) x[(size_t)blockIdx.y * lr2 + idx] = d.c == 1 ? cast_grey(g_lr[s_lr], mul, scale) : cast_rgb(f_lr[s_lr], mul, scale);
+}
+
+static unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
+
+// the (in, out) table of resample_table with its 8-bpc form (Resample.c normalize_coeffs_8bpc), made on first use
+int resample_table8(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::ResampleTable** out) {
+    const dcscn_ctx::ResampleTable* t;
+    int rc = resample_table(h, in_size, out_size, &t);
+    if (rc) return rc;
+    dcscn_ctx::ResampleTable& e = h->resample_tables[std::make_pair(in_size, out_size)];
+    if (!e.d_k8) {
+        std::vector<int> bounds;
+        std::vector<double> kk;
+        resample_coeffs(in_size, out_size, &bounds, &kk);
+        std::vector<int> k8(kk.size());
+        for (size_t i = 0; i < kk.size(); ++i)
+            k8[i] = kk[i] < 0 ? (int)(-0.5 + kk[i] * (1 << kPrecisionBits)) : (int)(0.5 + kk[i] * (1 << kPrecisionBits));
+        if ((rc = upload(h, k8.data(), k8.size() * sizeof(int), (void**)&e.d_k8))) return rc;
+    }
+    *out = &e;
+    return DCSCN_OK;
+}
+
+// Pillow mode "L" resize of n uint8 images [H, W] -> [OH, OW]: horizontal pass into tmp [n, H, OW], then the vertical pass
+// (a pass whose size does not change is skipped, as resize_device does)
+int resize_device8(dcscn_ctx* h, const uint8_t* in, uint8_t* tmp, uint8_t* out, int n, int H, int W, int OH, int OW, hipStream_t st) {
+    if (n <= 0) return DCSCN_OK;
+    const uint8_t* src = in;
+    const dcscn_ctx::ResampleTable* t;
+    int rc;
+    if (OW != W) {
+        if ((rc = resample_table8(h, W, OW, &t))) return rc;
+        uint8_t* dst = OH != H ? tmp : out;
+        const long long rows = (long long)n * H;
+        hipLaunchKernelGGL(resample_h8_kernel, dim3(blocks(rows * OW)), dim3(256), 0, st, src, dst, t->d_bounds, t->d_k8, t->ksize, rows, W, OW);
+        HIP_TRY(h, hipGetLastError());
+        src = dst;
+    }
+    if (OH != H) {
+        if ((rc = resample_table8(h, H, OH, &t))) return rc;
+        hipLaunchKernelGGL(resample_v8_kernel, dim3(blocks((long long)n * OH * OW)), dim3(256), 0, st, src, out, t->d_bounds, t->d_k8, t->ksize, n, H, OH, OW);
+        HIP_TRY(h, hipGetLastError());
+    } else if (OW == W) {
+        HIP_TRY(h, hipMemcpyAsync(out, in, (size_t)n * H * W, hipMemcpyDeviceToDevice, st));
+    }
+    return DCSCN_OK;
+}
+
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace
+
+int check_patches(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value) {
+    if (!h->train) return fail(h, DCSCN_ERR_STATE, "training batch before dcscn_train_begin");
+    if (!p || n < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "training batch: %d patches (need >= 1 and a patch array)", n);
+    if (lr_size < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "training batch: lr_size %d < 1", lr_size);
+    if (!(max_value > 0.0) || !std::isfinite(max_value)) return fail(h, DCSCN_ERR_INVALID_ARG, "training batch: max_value %g is not > 0", max_value);
+    const int64_t hr = (int64_t)lr_size * h->cfg.scale;
+    const int count = h->batches ? (int)h->batches->images.size() : 0;
+    for (int i = 0; i < n; ++i) {
+        const dcscn_patch& q = p[i];
+        if (q.image < 0 || q.image >= count) return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: unknown image %d (%d added)", i, q.image, count);
+        if (q.fliplr != 0 && q.fliplr != 1) return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: fliplr %d is not 0 or 1", i, q.fliplr);
+        const TrainImage& im = h->batches->images[q.image];
+        if (q.top < 0 || q.left < 0 || q.top + hr > im.H || q.left + hr > im.W)
+            return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: the %lld x %lld crop at (top %d, left %d) is outside image %d (%d x %d)", i,
+                        (long long)hr, (long long)hr, q.top, q.left, q.image, im.H, im.W);
+    }
+    return DCSCN_OK;
+}
+
+// after check_patches; x [n, L, L], x2 and y_true [n, HR, HR] device buffers
+int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int L, double max_value, float* x, float* x2, float* y_true, hipStream_t st) {
+    TrainBatches* b = h->batches;
+    const int s = h->cfg.scale, HR = L * s;
+    const size_t hr2 = (size_t)HR * HR, lr2 = (size_t)L * L;
+    int n_f = 0, n_g = 0;
+    for (int i = 0; i < n; ++i) (b->images[p[i].image].C == 1 ? n_g : n_f) += 1;
+    // planes: float32 HR, LR, x2 of the RGB patches, then uint8 HR, h-pass rows, LR, x2 of the grey ones
+    size_t off[7], bytes = 0;
+    const size_t sizes[7] = {(size_t)n_f * hr2 * 4, (size_t)n_f * lr2 * 4, (size_t)n_f * hr2 * 4, (size_t)n_g * hr2, (size_t)n_g * HR * L,
+                             (size_t)n_g * lr2, (size_t)n_g * hr2};
+    for (int k = 0; k < 7; ++k) { off[k] = bytes; bytes += align256(sizes[k]); }
+    int rc = grow(h, &b->planes, &b->planes_cap, bytes / 4, st);
+    if (rc) return rc;
+    char* base = reinterpret_cast<char*>(b->planes);
+    float *f_hr = (float*)(base + off[0]), *f_lr = (float*)(base + off[1]), *f_x2 = (float*)(base + off[2]);
+    uint8_t *g_hr = (uint8_t*)(base + off[3]), *g_tmp = (uint8_t*)(base + off[4]), *g_lr = (uint8_t*)(base + off[5]), *g_x2 = (uint8_t*)(base + off[6]);
+    // ordered behind a forward / resize of this handle on another stream (resize_device's row buffer rs_tmp is shared)
+    if (h->has_last && h->last_stream != st) HIP_TRY(h, hipStreamWaitEvent(st, h->done_ev, 0));
+
+    const int mul = max_value != 255.0;        // load_batch_image scales only when max_value != 255
+    const double scale = max_value / 255.0;
+    std::vector<PatchChunk> chunks((n + kChunk - 1) / kChunk);
+    for (int i = 0, nf = 0, ng = 0; i < n; ++i) {
+        const TrainImage& im = b->images[p[i].image];
+        chunks[i / kChunk].p[i % kChunk] = PatchDesc{im.px, im.W, im.C, p[i].top, p[i].left, p[i].fliplr, im.C == 1 ? ng++ : nf++};
+    }
+    for (size_t c = 0; c < chunks.size(); ++c) {
+        const int cnt = std::min(kChunk, n - (int)c * kChunk);
+        hipLaunchKernelGGL(batch_gather_kernel, dim3(blocks((long long)hr2), cnt), dim3(256), 0, st, chunks[c], HR, mul, scale, f_hr, g_hr,
+                           y_true + c * kChunk * hr2);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if ((rc = resize_device(h, f_hr, f_lr, n_f, HR, HR, L, L, st))) return rc;
+    if ((rc = resize_device(h, f_lr, f_x2, n_f, L, L, HR, HR, st))) return rc;
+    if ((rc = resize_device8(h, g_hr, g_tmp, g_lr, n_g, HR, HR, L, L, st))) return rc;
+    if ((rc = resize_device8(h, g_lr, g_tmp, g_x2, n_g, L, L, HR, HR, st))) return rc;
+    for (size_t c = 0; c < chunks.size(); ++c) {
+        const int cnt = std::min(kChunk, n - (int)c * kChunk);
+        hipLaunchKernelGGL(batch_finish_kernel, dim3(blocks((long long)hr2), cnt), dim3(256), 0, st, chunks[c], L, HR, mul, scale, f_lr, f_x2,
+                           g_lr, g_x2, x + c * kChunk * lr2, x2 + c * kChunk * hr2);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipEventRecord(h->done_ev, st));
+    h->last_stream = st;
+    h->has_last = true;
+    return DCSCN_OK;
+}
+
+void train_batches_free(dcscn_ctx* h) {
+    TrainBatches* b = h->batches;
+    if (!b) return;
+    for (TrainImage& im : b->images) (void)hipFree(im.px);
+    if (b->planes) (void)hipFree(b->planes);
+    if (b->out) (void)hipFree(b->out);
+    delete b;
+    h->batches = nullptr;
+}
+
+}  // namespace dcscn_impl
+
+extern "C" {
+
+int dcscn_train_add_image(dcscn_handle h, const uint8_t* pixels, int height, int width, int channels, int32_t* image_id) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!h->train) return fail(h, DCSCN_ERR_STATE, "dcscn_train_add_image before dcscn_train_begin");
+    if (!pixels || !image_id) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_add_image: null pointer");
+    if (height < 1 || width < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_add_image: bad size %d x %d", height, width);
+    if (channels != 1 && channels != 3)
+        return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_add_image: %d channels (images have 1 (grey) or 3 (RGB))", channels);
+    if (!h->batches) {
+        h->batches = new (std::nothrow) TrainBatches();
+        if (!h->batches) return fail(h, DCSCN_ERR_NOMEM, "out of host memory");
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    TrainImage im;
+    im.H = height; im.W = width; im.C = channels;
+    const size_t bytes = (size_t)height * width * channels;
+    hipError_t e = hipMalloc((void**)&im.px, bytes);
+    if (e != hipSuccess) return fail(h, DCSCN_ERR_NOMEM, "training image of %zu bytes: %s", bytes, hipGetErrorString(e));
+    e = hipMemcpy(im.px, pixels, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(im.px);
+        return fail(h, DCSCN_ERR_HIP, "dcscn_train_add_image: %s", hipGetErrorString(e));
+    }
+    h->batches->images.push_back(im);
+    *image_id = (int32_t)(h->batches->images.size() - 1);
+    return DCSCN_OK;
+}
+
+int dcscn_train_build_batch(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, float* x, float* x2, float* y_true) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    if (!x || !x2 || !y_true) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_build_batch: null output buffer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TrainBatches* b = h->batches;
+    const int s = h->cfg.scale;
+    const size_t lr_n = (size_t)n * lr_size * lr_size, hr_n = lr_n * s * s;
+    hipStream_t st = h->stream;
+    if ((rc = grow(h, &b->out, &b->out_cap, lr_n + 2 * hr_n, st))) return rc;
+    float *dx = b->out, *dx2 = dx + lr_n, *dy = dx2 + hr_n;
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, dx, dx2, dy, st))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(x, dx, lr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(x2, dx2, hr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(y_true, dy, hr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return DCSCN_OK;
+}
+
+}  // extern "C"

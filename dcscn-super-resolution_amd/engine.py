@@ -11,7 +11,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 MAX_NAME = 128
 
 ACTIVATORS = {None: 0, "": 0, "none": 0, "prelu": 1, "relu": 2, "leaky_relu": 3, "sigmoid": 4, "tanh": 5, "selu": 6}
@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "dcscn_resample_table", "dcscn_get_stream", "dcscn_synchronize", "dcscn_convert_rgb_to_y", "dcscn_convert_rgb_to_ycbcr",
     "dcscn_convert_y_and_cbcr_to_rgb", "dcscn_evaluate_rgb", "dcscn_sr_rgb",
     "dcscn_train_begin", "dcscn_train_step", "dcscn_train_step_device", "dcscn_train_gradients", "dcscn_get_tensor",
-    "dcscn_set_train_tensor",
+    "dcscn_set_train_tensor", "dcscn_train_add_image", "dcscn_train_build_batch", "dcscn_train_step_patches",
 )
 
 # dcscn_optimizer; the names of helper/args.py --optimizer
@@ -182,6 +182,9 @@ def load_library():
     lib.dcscn_train_gradients.argtypes = [vp, fp, fp, fp, c.c_int, c.c_int, c.c_int, c.c_uint64, dp]
     lib.dcscn_get_tensor.argtypes = [vp, c.c_char_p, fp, c.c_int64]
     lib.dcscn_set_train_tensor.argtypes = [vp, c.c_char_p, fp, c.c_int64]
+    lib.dcscn_train_add_image.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int32)]
+    lib.dcscn_train_build_batch.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, fp, fp, fp]
+    lib.dcscn_train_step_patches.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_double, c.c_uint64, dp]
     if lib.dcscn_abi_version() != ABI_VERSION:
         raise EngineError(5, "ABI mismatch: library %d, binding %d" % (lib.dcscn_abi_version(), ABI_VERSION))
     _lib = lib
@@ -492,6 +495,46 @@ class Engine:
                                                       int(n), int(h), int(w), float(lr), int(dropout_key) & (2 ** 64 - 1), stats,
                                                       ctypes.c_void_p(stream) if stream else None))
         return tuple(stats) if want_stats else None
+
+    def train_add_image(self, image):
+        """Upload a uint8 image [h, w, 1 | 3] (or [h, w]) for train_build_batch / train_step_patches; returns its image id.
+        It stays on the device until the engine is closed."""
+        a = np.ascontiguousarray(image)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise EngineError(1, "expected a uint8 image [h, w, 1] or [h, w, 3], got %s %s" % (a.dtype, a.shape))
+        image_id = ctypes.c_int32()
+        self._check(self._lib.dcscn_train_add_image(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), a.shape[0], a.shape[1],
+                                                    a.shape[2], ctypes.byref(image_id)))
+        return image_id.value
+
+    @staticmethod
+    def _patches(patches):
+        """dcscn_patch array from (image id, top, left, fliplr) rows."""
+        p = np.ascontiguousarray(np.asarray(patches, dtype=np.int32).reshape(-1, 4))
+        return p, ctypes.c_void_p(p.ctypes.data)
+
+    def train_build_batch(self, patches, lr_size, max_value=255.0):
+        """The batch of (image id, top, left, fliplr) patches as helper/loader.py's load_batch_image builds it, on the device:
+        float32 (x [n, lr_size, lr_size, 1], x2 [n, hr, hr, 1], y_true [n, hr, hr, 1]) with hr = lr_size * scale."""
+        p, ptr = self._patches(patches)
+        n, lr, hr = len(p), int(lr_size), int(lr_size) * self.scale
+        x = np.empty((n, lr, lr, 1), np.float32)
+        x2 = np.empty((n, hr, hr, 1), np.float32)
+        y = np.empty((n, hr, hr, 1), np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        self._check(self._lib.dcscn_train_build_batch(self._h, ptr, n, lr, float(max_value), x.ctypes.data_as(fp), x2.ctypes.data_as(fp),
+                                                      y.ctypes.data_as(fp)))
+        return x, x2, y
+
+    def train_step_patches(self, patches, lr_size, lr, max_value=255.0, dropout_key=0):
+        """train_step on the batch train_build_batch would build, built on the device; returns the stats of train_step."""
+        p, ptr = self._patches(patches)
+        stats = (ctypes.c_double * 4)()
+        self._check(self._lib.dcscn_train_step_patches(self._h, ptr, len(p), int(lr_size), float(max_value), float(lr),
+                                                       int(dropout_key) & (2 ** 64 - 1), stats))
+        return tuple(stats)
 
     def _numel(self, name):
         base = name

@@ -123,6 +123,8 @@ class SuperResolution:
         self.dropout_seed = 0
         self._train_flags = None            # build_optimizer
         self._train_engine = None           # the engine training was begun on
+        self._device_images = {}            # filename -> image id of the images uploaded to _train_engine
+        self._patches = None                # the batch build_input_batch drew, for the next train_batch
         self._pending_slots = None          # optimizer slots of a checkpoint loaded before training began
 
         self.name = self.get_model_name(model_name)
@@ -370,6 +372,7 @@ class SuperResolution:
         if self._train_engine is not eng:
             eng.train_begin(self._train_flags)
             self._train_engine = eng
+            self._device_images = {}
             if self._pending_slots:
                 for name, value in self._pending_slots.items():
                     eng.set_train_tensor(name, value)
@@ -401,8 +404,11 @@ class SuperResolution:
         self.train.init_batch_index()
 
     def build_input_batch(self):
-        for i in range(self.batch_num):
-            self.batch_input[i], self.batch_input_bicubic[i], self.batch_true[i] = self.train.load_batch_image(self.max_value)
+        """Draws the next batch_num patches (helper/loader.py next_patch); the next train_batch cuts them on the device, with
+        the results load_batch_image gives on the host."""
+        if self.channels != 1:
+            raise NotImplementedError("training batches are built for channels = 1 (Y) only")
+        self._patches = [self.train.next_patch() for _ in range(self.batch_num)]
 
     def dropout_key(self):
         return (int(self.dropout_seed) << 32) + int(self.step)
@@ -410,10 +416,21 @@ class SuperResolution:
     def train_batch(self):
         """One optimizer step on the current batch (sess.run(training_optimizer, ...), DCSCN.py:426-436)."""
         eng = self._ready_training()
-        x = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input])
-        x2 = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input_bicubic])
-        y = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_true])
-        image_loss, mse, _, _ = eng.train_step(x, x2, y, self.lr, dropout_key=self.dropout_key())
+        if self._patches is not None:      # drawn by build_input_batch: built on the device from the uploaded images
+            patches, self._patches = self._patches, None
+            descriptors = []
+            for filename, top, left, fliplr in patches:
+                image_id = self._device_images.get(filename)
+                if image_id is None:
+                    image_id = self._device_images[filename] = eng.train_add_image(self.train.image(filename))
+                descriptors.append((image_id, top, left, fliplr))
+            image_loss, mse, _, _ = eng.train_step_patches(descriptors, self.train.batch_image_size, self.lr, max_value=self.max_value,
+                                                           dropout_key=self.dropout_key())
+        else:                              # arrays assigned to batch_input, batch_input_bicubic, batch_true
+            x = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input])
+            x2 = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input_bicubic])
+            y = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_true])
+            image_loss, mse, _, _ = eng.train_step(x, x2, y, self.lr, dropout_key=self.dropout_key())
         self.training_loss_sum += image_loss
         self.training_psnr_sum += 0 if mse == 0 else 20 * math.log(self.max_value / math.sqrt(mse), 10)
         self.training_step += 1

@@ -32,7 +32,7 @@ class DynamicDataSets:
     """Random patches of the images of a directory (loader.py:278-355), with the reference's sequence of ``random``
     calls: a shuffled image order (random.sample), a crop of batch_image_size * scale (randrange per axis), fliplr with
     probability 1/2 (randrange(2)), then the LR and bicubic images by util.resize_image_by_pil.  Decoded images are
-    cached in memory."""
+    cached in memory.  next_patch() draws a patch's descriptor only; load_batch_image() cuts it on the host."""
 
     def __init__(self, scale, batch_image_size, channels=1, resampling_method="bicubic"):
         self.scale = scale
@@ -63,11 +63,35 @@ class DynamicDataSets:
         self.index += 1
         return image_no
 
+    def next_patch(self):
+        """(filename, top, left, fliplr) of the next patch: the image of the shuffled order (skipping images smaller than a
+        patch), a crop of batch_image_size * scale pixels at (top, left), then fliplr with probability 1/2 -- the reference's
+        sequence of random calls, which load_batch_image cuts on the host and SuperResolution.train_batch on the device."""
+        size = self.batch_image_size * self.scale
+        while True:
+            filename = self.filenames[self.get_next_image_no()]
+            height, width = self.image(filename).shape[0:2]
+            if height >= size and width >= size:
+                break
+            print("Error: %s should have more than %d x %d size." % (filename, size, size))
+        top = 0 if height == size else random.randrange(height - size)
+        left = 0 if width == size else random.randrange(width - size)
+        return filename, top, left, int(random.randrange(2) == 0)
+
+    def image(self, filename):
+        """The decoded image (uint8 [H, W, 1 | 3]), cached."""
+        image = self._cache.get(filename)
+        if image is None:
+            image = util.load_image(filename, print_console=False)
+            self._cache[filename] = image
+        return image
+
     def load_batch_image(self, max_value):
-        image = None
-        while image is None:
-            image = self.load_random_patch(self.filenames[self.get_next_image_no()])
-        if random.randrange(2) == 0:
+        filename, top, left, fliplr = self.next_patch()
+        size = self.batch_image_size * self.scale
+        image = self.image(filename)[top:top + size, left:left + size, :]
+        image = build_input_image(image, channels=self.channels, convert_ycbcr=True)
+        if fliplr:
             image = np.fliplr(image)
         input_image = util.resize_image_by_pil(image, 1 / self.scale, resampling_method=self.resampling_method)
         input_bicubic_image = util.resize_image_by_pil(input_image, self.scale, resampling_method=self.resampling_method)
@@ -77,21 +101,6 @@ class DynamicDataSets:
             input_bicubic_image = np.multiply(input_bicubic_image, scale)
             image = np.multiply(image, scale)
         return input_image, input_bicubic_image, image
-
-    def load_random_patch(self, filename):
-        image = self._cache.get(filename)
-        if image is None:
-            image = util.load_image(filename, print_console=False)
-            self._cache[filename] = image
-        height, width = image.shape[0:2]
-        load_batch_size = self.batch_image_size * self.scale
-        if height < load_batch_size or width < load_batch_size:
-            print("Error: %s should have more than %d x %d size." % (filename, load_batch_size, load_batch_size))
-            return None
-        y = 0 if height == load_batch_size else random.randrange(height - load_batch_size)
-        x = 0 if width == load_batch_size else random.randrange(width - load_batch_size)
-        image = image[y:y + load_batch_size, x:x + load_batch_size, :]
-        return build_input_image(image, channels=self.channels, convert_ycbcr=True)
 
 
 class BatchDataSets:

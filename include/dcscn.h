@@ -17,6 +17,7 @@
  *   sess.close()                                                    dcscn_destroy
  *   build_optimizer                         (DCSCN.py:379-413)      dcscn_train_begin
  *   sess.run(training_optimizer, ...)       (DCSCN.py:727-769)      dcscn_train_step / dcscn_train_step_device
+ *   DynamicDataSets.load_batch_image        (loader.py:278-355)     dcscn_train_add_image + dcscn_train_step_patches
  *   Saver.save / restore of the slots       (tf_graph.py:251-280)   dcscn_get_tensor / dcscn_set_train_tensor
  *
  * Conventions: plain C types only; all image tensors are dense NHWC float32 with C == 1
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DCSCN_ABI_VERSION 2
+#define DCSCN_ABI_VERSION 3
 #define DCSCN_MAX_NAME 128
 
 typedef struct dcscn_ctx* dcscn_handle;
@@ -380,6 +381,30 @@ int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, con
 /* Forward and backward only (gradients readable as "<var>/grad"); no update, slots untouched.  Host buffers. */
 int dcscn_train_gradients(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width,
                           uint64_t dropout_key, double* stats);
+
+/* Training batches built on the device from device-resident images (helper/loader.py DynamicDataSets.load_batch_image).
+ * A patch is a crop of HR = lr_size * scale pixels per side at (top, left) of an image added with dcscn_train_add_image, mirrored
+ * left-right when fliplr = 1.  Per patch, bit for bit what the host loader returns after the float32 cast of train_batch:
+ *   RGB image:  y = Y of the crop (float64, color.hip's chain), x = Pillow mode-"F" bicubic of float32(y) to lr_size, x2 = mode "F"
+ *               bicubic of x back to HR;  max_value != 255: y * (max_value / 255) in float64, x and x2 * float32(max_value / 255)
+ *   grey image: y = the uint8 pixels, x and x2 = Pillow mode-"L" (8-bit fixed-point) bicubic;  max_value != 255: all three
+ *               * (max_value / 255) in float64
+ * then the float32 cast.  One batch may mix grey and RGB patches.  Bad input (an unknown image, a crop outside its image,
+ * fliplr not 0 / 1, lr_size < 1, max_value <= 0) returns DCSCN_ERR_INVALID_ARG naming the patch; any of these calls before
+ * dcscn_train_begin returns DCSCN_ERR_STATE. */
+typedef struct dcscn_patch {
+    int32_t image, top, left, fliplr;
+} dcscn_patch;
+/* Upload an image (uint8 [height, width, channels], channels 1 or 3) once; it stays on the device until the handle is destroyed.
+ * *image_id receives its index for dcscn_patch.image (0, 1, 2, ... in call order). */
+int dcscn_train_add_image(dcscn_handle h, const uint8_t* pixels, int height, int width, int channels, int32_t* image_id);
+/* Build the batch of n patches into host buffers x [n, lr_size, lr_size], x2 and y_true [n, HR, HR]; synchronous. */
+int dcscn_train_build_batch(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, float* x, float* x2,
+                            float* y_true);
+/* Build the batch into the training workspace and take one step on it as dcscn_train_step does, on the handle's stream; no pixel
+ * crosses PCIe.  Synchronises only when stats != NULL (the 4 doubles of dcscn_train_step). */
+int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr,
+                             uint64_t dropout_key, double* stats);
 /* Read a variable (any time after its dcscn_set_tensor; the trained value while training), a gradient or a slot: `count`
  * must equal its number of values. */
 int dcscn_get_tensor(dcscn_handle h, const char* name, float* out, int64_t count);

@@ -6,6 +6,14 @@ into forward / dgrad / wgrad / loss / optimizer comes from a separate profiler r
 (tools/summarize_train_prof.py groups the kernel names).
 
     python tools/train_bench.py --config L7_x2 --batch 20 --size 48
+
+--loop times train.py's loop body instead, build_input_batch() + train_batch() of SuperResolution over Set14, for c-DCSCN x2
+(20 x 48^2), L12 x2 (20 x 48^2) and c-DCSCN x4 (20 x 32^2): host batches (the arrays of helper/loader.py load_batch_image,
+stepped with dcscn_train_step) against device batches (patch descriptors, dcscn_train_step_patches), alternating step by step in
+one process, each timed on the host clock up to the step's stats read-back; one JSON line per net, with the bare
+dcscn_train_step_device time of the same batch shape for scale.  --device-only runs only the device leg (profiler runs).
+
+    python tools/train_bench.py --loop
 """
 import argparse
 import json
@@ -27,7 +35,10 @@ CONFIGS = {
     "L7_x2": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
                   reconstruct_layers=0, pixel_shuffler_filters=1),
     "L12_x2": dict(),
+    "L7_x4": dict(scale=4, layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
+                  reconstruct_layers=0, pixel_shuffler_filters=1),
 }
+LOOP_CASES = (("L7_x2", 20, 48), ("L12_x2", 20, 48), ("L7_x4", 20, 32))
 PEAK_F32_MATRIX = 157.3e12
 
 
@@ -134,6 +145,56 @@ def bench_torch(cfg, n, h, w, steps, warmup):
     return float(np.median(times))
 
 
+def loop_model(name, n, size, tmp):
+    from dcscn_amd.model import SuperResolution
+    from helper import args
+    f = {k: args.FLAGS._flags[k].default for k in args.FLAGS}
+    f.update(CONFIGS[name], self_ensemble=1, batch_num=n, batch_image_size=size, checkpoint_dir=tmp, log_filename="", **flags())
+    m = SuperResolution(type("Flags", (dict,), {"__getattr__": dict.__getitem__})(f))
+    m.build_graph()
+    m.build_optimizer()
+    m.load_weights(O.synthetic_weights(O.make_config(**CONFIGS[name]), seed=0))
+    m.load_dynamic_datasets(os.path.join(ROOT, "tests", "golden", "set14"), size)
+    m.init_train_step()
+    m.init_epoch_index()
+    return m
+
+
+def host_batch(m):
+    """build_input_batch before device batches: every patch cut and resized on the host."""
+    for i in range(m.batch_num):
+        m.batch_input[i], m.batch_input_bicubic[i], m.batch_true[i] = m.train.load_batch_image(m.max_value)
+
+
+def bench_loop(name, n, size, steps, warmup, device_only):
+    import random
+    import tempfile
+    import time
+    random.seed(0)
+    legs = {"device": lambda m: m.build_input_batch()}
+    if not device_only:
+        legs["host"] = host_batch
+    with tempfile.TemporaryDirectory() as tmp:
+        models = {k: loop_model(name, n, size, os.path.join(tmp, k)) for k in legs}
+        times = {k: [] for k in legs}
+        for i in range(warmup + steps):           # warm-up: every image decoded (and uploaded) at least once
+            for k, draw in legs.items():
+                t0 = time.perf_counter()
+                draw(models[k])
+                models[k].train_batch()           # returns after the step's stats are on the host
+                if i >= warmup:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+        for m in models.values():
+            m.close()
+    out = dict(loop=name, batch=n, lr_size=size, steps=steps, warmup=warmup, device_batches_ms=round(float(np.median(times["device"])), 4))
+    if not device_only:
+        bare, _ = bench_hip(O.make_config(**CONFIGS[name]), n, size, size, steps, warmup)
+        out.update(host_batches_ms=round(float(np.median(times["host"])), 4), bare_train_step_device_ms=round(bare, 4),
+                   device_over_bare=round(out["device_batches_ms"] / bare, 3),
+                   host_over_device=round(float(np.median(times["host"])) / out["device_batches_ms"], 2))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="L7_x2", choices=sorted(CONFIGS))
@@ -143,7 +204,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison (profiler runs)")
     ap.add_argument("--torch-only", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--loop", action="store_true", help="time build_input_batch() + train_batch() with host and device batches")
+    ap.add_argument("--device-only", action="store_true", help="--loop: the device-batch leg only (profiler runs)")
     a = ap.parse_args()
+    if a.loop:
+        for name, n, size in LOOP_CASES:
+            print(json.dumps(bench_loop(name, n, size, a.steps, a.warmup, a.device_only)), flush=True)
+        return
     cfg = O.make_config(**CONFIGS[a.config])
     if a.torch_only:
         print(json.dumps({"torch_ms_per_step": bench_torch(cfg, a.batch, a.size, a.size, a.steps, a.warmup)}))
