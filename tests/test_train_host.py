@@ -48,14 +48,10 @@ def test_restatement_forward_matches_the_float64_torch_model(oracle):
         assert np.max(np.abs(y - ref)) <= 1e-9 * max(1.0, np.max(np.abs(ref))), over
 
 
-def test_restatement_gradient_matches_finite_differences(oracle):
-    cfg = oracle.make_config(layers=3, filters=6, min_filters=4, nin_filters=4, nin_filters2=3, reconstruct_layers=2,
-                             reconstruct_filters=3, scale=2)
-    w = oracle.synthetic_weights(cfg, seed=1)
-    x, x2 = synthetic_batch(1, 6, 6, 2, seed=2)
-    y_true = x2 + np.random.default_rng(0).normal(0, 5, x2.shape).astype(np.float32)
+def _assert_matches_finite_differences(cfg, w, x, x2, y_true, names):
+    """Element 0 of every tensor in ``names``: autograd against the central difference of the float64 loss."""
     _, g = R.loss_and_grads(cfg, w, x, x2, y_true, l2_decay=1e-3)
-    for name in ("CNN2/conv_W", "B2/conv_B", "A1/prelu/A1_prelu", "Up-PS/Up-PS_CNN/conv_W", "R-CNN1/conv_W"):
+    for name in names:
         w2 = {k: np.asarray(v, np.float64).copy() for k, v in w.items()}
         idx = (0,) * w2[name].ndim
         h = 1e-6
@@ -65,6 +61,38 @@ def test_restatement_gradient_matches_finite_differences(oracle):
         lm = R.loss_and_grads(cfg, w2, x, x2, y_true, l2_decay=1e-3)[0]["loss"]
         fd = (lp - lm) / (2 * h)
         assert abs(fd - g[name][idx]) <= 1e-5 * max(1.0, abs(fd)), (name, fd, g[name][idx])
+
+
+def test_restatement_gradient_matches_finite_differences(oracle):
+    base = dict(layers=3, filters=6, min_filters=4, nin_filters=4, nin_filters2=3, reconstruct_layers=2, reconstruct_filters=3, scale=2)
+    for act in ("prelu", "relu", "leaky_relu", "sigmoid", "tanh", "selu"):
+        cfg = oracle.make_config(**dict(base, activator=act))
+        w = oracle.synthetic_weights(cfg, seed=1)
+        x, x2 = synthetic_batch(1, 6, 6, 2, seed=2)
+        if act in ("sigmoid", "tanh", "selu"):
+            x = x / np.float32(255.0)                               # off saturation, as the device tests feed these activators
+        y_true = x2 + np.random.default_rng(0).normal(0, 5, x2.shape).astype(np.float32)
+        names = ["CNN2/conv_W", "B2/conv_B", "Up-PS/Up-PS_CNN/conv_W", "R-CNN1/conv_W"] + (["A1/prelu/A1_prelu"] if act == "prelu" else [])
+        _assert_matches_finite_differences(cfg, w, x, x2, y_true, names)
+
+
+def test_restatement_gradient_on_formerly_refused_and_one_channel_nets(oracle):
+    """loss_and_grads raised 'grad_weight must be contiguous' on the first two of these (a permuted weight view handed to conv2d);
+    the third has one-channel layers (min_filters = 1) with NIN."""
+    cases = [(dict(layers=3, filters=24, min_filters=1, filters_decay_gamma=2.0, use_nin=False, pixel_shuffler_filters=16), (1, 2, 20),
+              ("CNN3/conv_W", "C/conv_B", "Up-PS/Up-PS_CNN/conv_W")),
+             (dict(layers=2, filters=52, min_filters=4, filters_decay_gamma=1.5, use_nin=False, reconstruct_layers=3, reconstruct_filters=32,
+                   pixel_shuffler_filters=1), (4, 17, 10), ("CNN2/conv_W", "C/prelu/C_prelu", "R-CNN2/conv_W")),
+             (dict(layers=4, filters=9, min_filters=1, filters_decay_gamma=2.0, nin_filters=9, nin_filters2=3, scale=3), (2, 5, 4),
+              ("CNN4/conv_W", "CNN4/prelu/CNN4_prelu", "B2/conv_W"))]
+    for over, (n, h, wd), names in cases:
+        cfg = oracle.make_config(**over)
+        w = oracle.synthetic_weights(cfg, seed=1)
+        x, x2 = synthetic_batch(n, h, wd, cfg["scale"], seed=2)
+        y_true = x2 + np.random.default_rng(0).normal(0, 5, x2.shape).astype(np.float32)
+        _, g = R.loss_and_grads(cfg, w, x, x2, y_true, l2_decay=1e-3)
+        assert set(g) == set(w) and all(np.isfinite(v).all() and v.shape == w[k].shape for k, v in g.items())
+        _assert_matches_finite_differences(cfg, w, x, x2, y_true, names)
 
 
 def test_checkpoint_with_adam_slots_round_trips(oracle):

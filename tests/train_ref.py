@@ -56,7 +56,7 @@ def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64):
         kind = op["op"]
         if kind == "conv":
             v, k = op["var"], op["k"]
-            w = leaves[v + "/conv_W"].permute(3, 2, 0, 1)
+            w = leaves[v + "/conv_W"].permute(3, 2, 0, 1).contiguous()     # (slow_conv2d's backward refuses some permuted views)
             h = F.conv2d(t[op["src"]], w, padding=k // 2)
             if op["bias"]:
                 h = h + leaves[v + "/conv_B"].view(1, -1, 1, 1)
