@@ -225,7 +225,6 @@ int dcscn_finalize(dcscn_handle h) {
             if (rc) return rc;
         }
     }
-    h->prof_ms.assign(h->ops.size(), 0.0);
     h->finalized = true;
     return DCSCN_OK;
 }
@@ -248,15 +247,11 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out) {
     memset(out, 0, sizeof *out);
     snprintf(out->name, sizeof out->name, "%s", op.name.c_str());
     const bool s16 = op_on_split16(h, op);
-    const bool h8 = op_takes_h8(h, op);                          // (the predicate launch_op itself uses)
-    snprintf(out->kernel, sizeof out->kernel, "%s", op.kind == OP_CONV ? (s16 ? (op.shape.nin ? "conv_nin_h" : op.fold_s > 0 ? "conv5_h" : h8 ? "conv3_h8" : "conv3_h") : op.shape.wino ? "conv_wino2" : op.shape.nin ? "conv_nin" : "conv_igemm") : op.kind == OP_CIN1 ? "conv_cin1" : op.kind == OP_COUT1 ? "conv_cout1" : op.kind == OP_STREAM ? "feat_stream" : op.kind == OP_TAIL ? "tail_stream" : op.kind == OP_STREAM3 ? (s16 ? "feat3_stream" : "layer by layer") : op.kind == OP_FOLDX ? (s16 ? "conv5_h" : "layer by layer") : "depthwise");
+    snprintf(out->kernel, sizeof out->kernel, "%s", kernel_name(op_kernel(h, op)));      // (the decision launch_op itself takes)
     out->kernel_size = op.ks;
     out->in_channels = op.cin;
     out->out_channels = op.cout;
     out->resolution = op.res;
-    if (op.kind == OP_CONV && h->finalized) {
-        out->mt = op.shape.mt; out->nt = op.shape.nt; out->kc = op.shape.kc; out->n_tiles = op.n_tiles;
-    }
     out->macs_per_lr_pixel = op.macs;
     out->bytes_per_lr_pixel = op.bytes;
     out->executed_macs_per_lr_pixel = op.macs;
@@ -265,6 +260,7 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out) {
         out->executed_macs_per_lr_pixel = 3 * 25 * (int64_t)op.h16.n_chunks * 32 * 16;      // (the border ring's launch repeats 8 % of it on a 48 x 48 patch)
     }
     if (op.kind == OP_CONV && h->finalized) {
+        out->mt = op.shape.mt; out->nt = op.shape.nt; out->kc = op.shape.kc; out->n_tiles = op.n_tiles;
         const int64_t r2 = (int64_t)op.res * op.res;
         const int64_t k_exec = (int64_t)op.n_chunks * op.shape.kc;             // padded input channels
         if (s16) {
@@ -299,7 +295,6 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
     if (!strcmp(key, "workspace_budget_bytes")) {
         if (value < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "workspace_budget_bytes must be >= 1");
         h->workspace_budget = value;
-        h->budget_user_set = true;
         return DCSCN_OK;
     }
     if (!strcmp(key, "spatial_tiling")) {
@@ -401,24 +396,12 @@ int dcscn_forward_device(dcscn_handle h, const float* x, const float* x2, float*
     return run_forward(h, x, x2, y, n, height, width, stream ? (hipStream_t)stream : h->stream);
 }
 
+// (a failed allocation of the host-path staging has always been DCSCN_ERR_HIP)
 static int ensure_io(dcscn_ctx* h, size_t lr_floats, size_t hr_floats) {
-    if (lr_floats > h->io_x_cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->io_x) HIP_TRY(h, hipFree(h->io_x));
-        h->io_x = nullptr; h->io_x_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->io_x, lr_floats * sizeof(float)));
-        h->io_x_cap = lr_floats;
-    }
-    if (hr_floats > h->io_y_cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->io_x2) HIP_TRY(h, hipFree(h->io_x2));
-        if (h->io_y) HIP_TRY(h, hipFree(h->io_y));
-        h->io_x2 = h->io_y = nullptr; h->io_y_cap = 0;
-        HIP_TRY(h, hipMalloc((void**)&h->io_x2, hr_floats * sizeof(float)));
-        HIP_TRY(h, hipMalloc((void**)&h->io_y, hr_floats * sizeof(float)));
-        h->io_y_cap = hr_floats;
-    }
-    return DCSCN_OK;
+    int rc = grow(h, &h->io_x, &h->io_x_cap, lr_floats, h->stream, DCSCN_ERR_HIP);
+    if (!rc) rc = grow(h, &h->io_x2, &h->io_x2_cap, hr_floats, h->stream, DCSCN_ERR_HIP);
+    if (!rc) rc = grow(h, &h->io_y, &h->io_y_cap, hr_floats, h->stream, DCSCN_ERR_HIP);
+    return rc;
 }
 
 // Host-buffer forward in up to 4 chunks of images: the upload of chunk i+1 and the download of chunk i-1 run while chunk i
@@ -520,10 +503,7 @@ int dcscn_resize_bicubic_device(dcscn_handle h, const float* in, float* out, int
     if (h->has_last && h->last_stream != st) HIP_TRY(h, hipStreamWaitEvent(st, h->done_ev, 0));
     const int rc = resize_device(h, in, out, n, height, width, out_height, out_width, st);
     if (rc) return rc;
-    HIP_TRY(h, hipEventRecord(h->done_ev, st));
-    h->last_stream = st;
-    h->has_last = true;
-    return DCSCN_OK;
+    return forward_done(h, st);
 }
 
 int dcscn_forward_lr(dcscn_handle h, const float* x, float* y, int n, int height, int width) {
@@ -798,12 +778,9 @@ int dcscn_destroy(dcscn_handle h) {
     if (h->arena) (void)hipFree(h->arena);
     if (h->d_zrec) (void)hipFree(h->d_zrec);
     if (h->d_digest) (void)hipFree(h->d_digest);
-    for (float* p : {h->tile_x, h->tile_x2, h->tile_y, h->rs_tmp, h->rs_in, h->rs_out, h->ens_x, h->ens_x2, h->ens_y, h->ens_out, h->col_rgb, h->col_d,
+    for (float* p : {h->io_x, h->io_x2, h->io_y, h->tile_x, h->tile_x2, h->tile_y, h->rs_tmp, h->rs_in, h->rs_out, h->ens_x, h->ens_x2, h->ens_y, h->ens_out, h->col_rgb, h->col_d,
                      h->col_d2, h->col_y32})
         if (p) (void)hipFree(p);
-    if (h->io_x) (void)hipFree(h->io_x);
-    if (h->io_x2) (void)hipFree(h->io_x2);
-    if (h->io_y) (void)hipFree(h->io_y);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return DCSCN_OK;

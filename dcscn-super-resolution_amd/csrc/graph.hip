@@ -39,7 +39,7 @@ int add_tensor(dcscn_ctx* h, const std::string& name, std::vector<int64_t> shape
     return (int)h->tensors.size() - 1;
 }
 
-int new_buf(dcscn_ctx* h, int stride, int res) {
+static int new_buf(dcscn_ctx* h, int stride, int res) {
     WsBuf b;
     b.stride = stride;
     b.res = res;
@@ -143,28 +143,7 @@ void add_conv(dcscn_ctx* h, const std::string& var, const std::string& short_nam
     op.vec4 = out_stride % 4 == 0 && dst.off % 4 == 0 && dst.width % 4 == 0 && (dst.ps == 1 || dst.ps_c % 4 == 0) &&
               !dst.residual;
     const int64_t out_bytes = 4 * r2 * dst.width;
-
-    if (ds && src.buf >= 0 && cin == 1 && cout == 1 && dst.buf == EXT_Y && !bias && activator == DCSCN_ACT_NONE &&
-        cout1_lds_bytes(ks, src.cin_phys) <= 64 * 1024) {
-        // separable 1 -> 1 conv (R-CNN of the c-DCSCN DS models): depthwise sum, times the pointwise
-        // scalar, plus the residual -- one launch of the single-output kernel
-        op.kind = OP_COUT1;
-        op.ks = ks;
-        op.cin = 1;
-        op.in_buf = src.buf;
-        op.in_off = src.off;
-        op.cin_phys = src.cin_phys;
-        op.chan_map = src.map;
-        op.dw_w = t_dw;
-        op.macs = li.macs_per_lr_pixel;
-        op.bytes = 4 * r2 * src.cin_phys + out_bytes + (dst.residual ? 4 * r2 : 0);
-    } else if (ds && src.buf >= 0 && ks == 3) {
-        // depthwise half fused into the staging of the pointwise GEMM: its output never touches HBM
-        // (instantiated for 1x1 / 3x3 depthwise filters; --cnn_size=5/7 separable models take the two-launch form below)
-        op.kind = OP_CONV;
-        op.ks = 1;
-        op.dwk = ks;
-        op.dw_w = t_dw;
+    auto reads_src = [&]() {              // the launch reads `src` itself, all of the layer's work is its own
         op.cin = cin;
         op.in_buf = src.buf;
         op.in_off = src.off;
@@ -172,6 +151,24 @@ void add_conv(dcscn_ctx* h, const std::string& var, const std::string& short_nam
         op.chan_map = src.map;
         op.macs = li.macs_per_lr_pixel;
         op.bytes = 4 * r2 * src.cin_phys + out_bytes + (dst.residual ? 4 * r2 : 0);
+    };
+
+    if (ds && src.buf >= 0 && cin == 1 && cout == 1 && dst.buf == EXT_Y && !bias && activator == DCSCN_ACT_NONE &&
+        cout1_lds_bytes(ks, src.cin_phys) <= 64 * 1024) {
+        // separable 1 -> 1 conv (R-CNN of the c-DCSCN DS models): depthwise sum, times the pointwise
+        // scalar, plus the residual -- one launch of the single-output kernel
+        op.kind = OP_COUT1;
+        op.ks = ks;
+        op.dw_w = t_dw;
+        reads_src();
+    } else if (ds && src.buf >= 0 && ks == 3) {
+        // depthwise half fused into the staging of the pointwise GEMM: its output never touches HBM
+        // (instantiated for 1x1 / 3x3 depthwise filters; --cnn_size=5/7 separable models take the two-launch form below)
+        op.kind = OP_CONV;
+        op.ks = 1;
+        op.dwk = ks;
+        op.dw_w = t_dw;
+        reads_src();
     } else if (ds) {
         // first layer (reads the 1-channel external input), or a 5x5 / 7x7 depthwise filter: depthwise half ->
         // DW scratch (logical channel order, zero padded to 4), then the pointwise GEMM
@@ -216,13 +213,7 @@ void add_conv(dcscn_ctx* h, const std::string& var, const std::string& short_nam
                           cout1_lds_bytes(ks, src.cin_phys) <= 64 * 1024;
         op.kind = to_y ? OP_COUT1 : OP_CONV;
         op.ks = ks;
-        op.cin = cin;
-        op.in_buf = src.buf;
-        op.in_off = src.off;
-        op.cin_phys = src.cin_phys;
-        op.chan_map = src.map;
-        op.macs = li.macs_per_lr_pixel;
-        op.bytes = 4 * r2 * src.cin_phys + out_bytes + (dst.residual ? 4 * r2 : 0);
+        reads_src();
     }
     h->ops.push_back(op);
 }
@@ -441,7 +432,7 @@ int build_graph(dcscn_ctx* h) {
 }
 
 // ---- Winograd plan ------------------------------------------------------------------------------------
-int op_tiles16(const Op& op) {
+static int op_tiles16(const Op& op) {
     int ctot = 0;
     for (const ColSeg& s : op.segs) ctot = std::max(ctot, s.dst + s.cout);
     return (ctot + 15) / 16;
@@ -474,6 +465,27 @@ bool wino_eligible(const dcscn_ctx* h, const Op& op) {
 bool h16_direct_eligible(const dcscn_ctx* h, const Op& op) {
     return h->winograd && !wino_eligible(h, op) && op.kind == OP_CONV && op.ks == 3 && op.dwk == 0 && op.cin_phys >= 24 && op.segs.size() == 1 &&
            op.tconv_s == 0 && op.fold_s == 0 && op.in_stride_override <= 0;
+}
+
+// The workspace tensors a launch reads: its multi-source list where it has one (densify_features: in_buf still names the concat tensor
+// the list replaced, which is not read), else in_buf.
+static std::vector<int> op_inputs(const Op& op) {
+    std::vector<int> v;
+    if (!op.multi.empty()) for (const auto& m : op.multi) v.push_back(m.first);
+    else if (op.in_buf >= 0) v.push_back(op.in_buf);
+    return v;
+}
+
+// A rewrite that removed launches leaves their tensors behind: a tensor that no launch of the plan reads (op_inputs) or writes
+// (for_each_dst) any more does not exist -- stride 0, no bytes in the carve.
+static void release_if_unused(dcscn_ctx* h, int buf) {
+    if (buf < 0) return;
+    bool used = false;
+    for (const Op& o : h->ops) {
+        for (int b : op_inputs(o)) used = used || b == buf;
+        for_each_dst(o, [&](int b, int) { used = used || b == buf; });
+    }
+    if (!used) h->bufs[buf].stride = 0;
 }
 
 // ---- optional graph rewrite: the linear tail as one conv ----------------------------------------
@@ -526,7 +538,7 @@ bool fold_linear_tail(dcscn_ctx* h) {
     f.out_off[0] = f.out_off[1] = 0;
     f.out_width[0] = 1;
     f.out_width[1] = 0;
-    f.split = 1 << 30;
+    f.split = kNoSplit;
     f.residual = true;
     f.vec4 = false;
     f.macs = u.macs + r.macs;                       // algorithmic work of the layers it replaces
@@ -535,9 +547,7 @@ bool fold_linear_tail(dcscn_ctx* h) {
     const int dead = u.out_buf[0];
     h->ops.pop_back();
     h->ops.pop_back();
-    bool used = false;
-    for (const Op& o : h->ops) used = used || o.in_buf == dead || o.out_buf[0] == dead || o.out_buf[1] == dead;
-    if (!used && dead >= 0) h->bufs[dead].stride = 0;   // the shuffled HR map no longer exists
+    release_if_unused(h, dead);                     // the shuffled HR map no longer exists
     h->ops.push_back(f);
     return true;
 }
@@ -610,7 +620,7 @@ int stream_chunk_channel(int quads, int ch, int q, int s) {
     return s == 0 ? 16 * ch + q : -1;
 }
 // the (input quads, output tiles) pairs stream_conv_role is instantiated for (feat_stream.hpp: feat_stream)
-bool stream_conv_supported(int in_quads, int out_tiles) {
+static bool stream_conv_supported(int in_quads, int out_tiles) {
     if (in_quads <= 5) return out_tiles == 1;
     if (in_quads <= 7) return out_tiles == 2;
     return true;
@@ -678,11 +688,7 @@ void fuse_feat_stream(dcscn_ctx* h) {
     const int t1 = nin.out_buf[0], cat = h->concat_buf;
     h->ops.erase(h->ops.begin(), h->ops.begin() + n_rep);
     h->ops.insert(h->ops.begin(), f);
-    for (int dead : {t1, cat, dw1.out_buf[0]}) {
-        bool used = false;
-        for (const Op& o : h->ops) used = used || o.in_buf == dead || o.out_buf[0] == dead || o.out_buf[1] == dead;
-        if (!used && dead >= 0) h->bufs[dead].stride = 0;
-    }
+    for (int dead : {t1, cat, dw1.out_buf[0]}) release_if_unused(h, dead);
     h->concat_buf = -1;                                    // nothing left for densify_features
 }
 
@@ -723,8 +729,7 @@ void fuse_tail_stream(dcscn_ctx* h) {
     const int dead[2] = {u1.out_buf[0], u2.out_buf[0]};
     h->ops.erase(h->ops.end() - 3, h->ops.end());
     h->ops.push_back(f);
-    for (int d : dead)
-        if (d >= 0) h->bufs[d].stride = 0;
+    for (int d : dead) release_if_unused(h, d);
 }
 
 
@@ -768,9 +773,7 @@ void densify_features(dcscn_ctx* h) {
         Op& op = h->ops[ci];
         for (size_t k = 0; k < nb.size(); ++k) op.multi.push_back({nb[k], pad4(h->concat_slices[k].second)});
     }
-    bool used = false;
-    for (const Op& o : h->ops) used = used || (o.multi.empty() && o.in_buf == cat) || o.out_buf[0] == cat || o.out_buf[1] == cat;
-    if (!used) h->bufs[cat].stride = 0;                         // the concat tensor no longer exists
+    release_if_unused(h, cat);                                  // the concat tensor no longer exists
 }
 
 // ---- row-streamed feature extractor of the non-separable narrow nets (feat3_stream.hpp) --------------------------------------
@@ -795,7 +798,7 @@ void fuse_feat3_stream(dcscn_ctx* h) {
         const Op& o = h->ops[i];
         if (o.kind != OP_CONV || o.ks != 3 || o.dwk != 0 || o.ps != 1 || o.residual || o.act != ACT_ALPHA || o.segs.size() != 1 || o.tconv_s > 0 || o.fold_s > 0 ||
             o.res != 1 || o.cin != h->sched[i - 1] || o.cout != h->sched[i] || o.in_buf != h->ops[i - 1].out_buf[0] || o.in_off != 0 || o.out_off[0] != 0 ||
-            o.out_buf[0] < 0 || o.split < (1 << 29) || !o.multi.empty())
+            o.out_buf[0] < 0 || has_second_dst(o) || !o.multi.empty())
             return;
         for (size_t k = 0; k < o.chan_map.size(); ++k)
             if (o.chan_map[k] != (int)k) return;
@@ -817,7 +820,7 @@ void fuse_feat3_stream(dcscn_ctx* h) {
         for (int i = 0; ok && i < L; ++i) ok = nin.multi[i].first == h->ops[i].out_buf[0];
         ok = ok && b2.kind == OP_CONV && b2.ks == 3 && b2.dwk == 0 && b2.cin == 8 && b2.cout == 8 && b2.act == ACT_ALPHA && b2.ps == 1 && !b2.residual &&
              b2.segs.size() == 1 && b2.in_buf == nin.out_buf[0] && b2.in_off == 0 && b2.out_buf[0] == nin.out_buf[1] && b2.out_off[0] == 0 &&
-             b2.split >= (1 << 29) && b2.tconv_s == 0 && b2.fold_s == 0 && b2.res == 1 && h->bufs[nin.out_buf[1]].stride == 32;
+             !has_second_dst(b2) && b2.tconv_s == 0 && b2.fold_s == 0 && b2.res == 1 && h->bufs[nin.out_buf[1]].stride == 32;
         // the pair roles are instantiated for: conv[L - 4] reads three octets, conv[L - 3] and conv[L - 2] two; one output tile each
         ok = ok && octs(L - 4) == 3 && octs(L - 3) == 2 && octs(L - 2) == 2 && h->sched[L - 3] <= 16 && h->sched[L - 2] <= 16 && h->sched[L - 1] <= 16;
         const size_t lds2 = lds + (size_t)4 * kStreamRowPx * (2 * octs(L - 1) + 1) * 16 + (size_t)4 * kStreamRowPx * 3 * 16;
@@ -863,13 +866,6 @@ void plan_p16(dcscn_ctx* h) {
     const size_t nbuf = h->bufs.size();
     std::vector<char> ok(nbuf, 0), written(nbuf, 0), read(nbuf, 0);
     for (size_t b = 0; b < nbuf; ++b) ok[b] = h->bufs[b].stride > 0;
-    const bool mixed = false;
-    auto inputs = [&](const Op& op) {
-        std::vector<int> v;
-        if (!op.multi.empty()) for (const auto& m : op.multi) v.push_back(m.first);
-        else if (op.in_buf >= 0) v.push_back(op.in_buf);
-        return v;
-    };
     auto can_read = [&](const Op& op) {
         if ((op.kind != OP_CONV && op.kind != OP_FOLDX) || !op.h16.on || op.dwk != 0 || op.in_stride_override > 0) return false;
         if (!op.multi.empty()) return op.shape.nin != 0;          // (the pad-8 virtual K axis of densify_features)
@@ -883,44 +879,38 @@ void plan_p16(dcscn_ctx* h) {
         if (op.kind == OP_CIN1) return k == 0 && op.out_off[0] == 0 && op.ks <= 3;   // (conv_cin1's octet-per-thread store path holds 2 x taps filter quads)
         if (op.kind != OP_CONV || !op.h16.on || op.fold_s > 0 || op.residual || op.dwk != 0) return false;
         // a pixel shuffler whose sub-pixels take whole 16-channel tiles (conv3_h's P16 epilogue with depth_to_space addressing): ONE destination
-        if (op.ps != 1 && (op.shape.nin || op.ps_c % 16 != 0 || k != 0 || op.split < (1 << 29))) return false;
+        if (op.ps != 1 && (op.shape.nin || op.ps_c % 16 != 0 || k != 0 || has_second_dst(op))) return false;
         if (op.out_off[k] % 16 != 0) return false;
         return k == 0 || op.split % 16 == 0;
     };
-    for (bool changed = !mixed; changed;) {
+    for (bool changed = true; changed;) {
         changed = false;
         for (const Op& op : h->ops) {
-            const std::vector<int> in = inputs(op);
+            const std::vector<int> in = op_inputs(op);
             bool all = can_read(op);
             for (int b : in) all = all && ok[b];
             if (!all)
                 for (int b : in)
                     if (ok[b]) { ok[b] = 0; changed = true; }
-            for (int k = 0; k < 2; ++k) {
-                const int b = op.out_buf[k];
-                if (b < 0 || (k == 1 && op.split >= (1 << 29))) continue;
-                if (ok[b] && !can_write(op, k)) { ok[b] = 0; changed = true; }
-            }
-            for (int b : op.extra_out)
-                if (ok[b] && !can_write(op, 0)) { ok[b] = 0; changed = true; }
+            for_each_dst(op, [&](int b, int k) {
+                if (b >= 0 && ok[b] && !can_write(op, k)) { ok[b] = 0; changed = true; }
+            });
         }
     }
     for (const Op& op : h->ops) {
-        for (int b : inputs(op)) read[b] = 1;
-        for (int k = 0; k < 2; ++k)
-            if (op.out_buf[k] >= 0 && !(k == 1 && op.split >= (1 << 29))) written[op.out_buf[k]] = 1;
-        for (int b : op.extra_out) written[b] = 1;
+        for (int b : op_inputs(op)) read[b] = 1;
+        for_each_dst(op, [&](int b, int) { if (b >= 0) written[b] = 1; });
     }
     h->any_p16 = false;
     h->p16_max_res = 1;
     for (size_t b = 0; b < nbuf; ++b) {
         WsBuf& wb = h->bufs[b];
-        wb.p16_ok = !mixed && ok[b] && written[b] && read[b];
+        wb.p16_ok = ok[b] && written[b] && read[b];
         wb.octs = (wb.stride + 7) / 8;
         if (wb.p16_ok) { h->any_p16 = true; h->p16_max_res = std::max(h->p16_max_res, wb.res); }
     }
     for (Op& op : h->ops) {
-        const std::vector<int> in = inputs(op);
+        const std::vector<int> in = op_inputs(op);
         bool all = !in.empty() && can_read(op);
         for (int b : in) all = all && h->bufs[b].p16_ok;
         op.h16.in16_ok = all;
@@ -929,16 +919,11 @@ void plan_p16(dcscn_ctx* h) {
     std::vector<char> dirty(nbuf, 0);
     for (Op& op : h->ops) {
         bool r = (op.kind == OP_CONV || op.kind == OP_STREAM || op.kind == OP_TAIL || op.kind == OP_STREAM3 || op.kind == OP_FOLDX) && op.h16.on;
-        for (int b : inputs(op)) r = r || dirty[b];
-        for (int k = 0; k < 2; ++k)
-            if (op.out_buf[k] >= 0 && !(k == 1 && op.split >= (1 << 29))) r = r || h->bufs[op.out_buf[k]].p16_ok;
+        for (int b : op_inputs(op)) r = r || dirty[b];
+        // (extra_out included: such a tensor is P16 only where the launch's own split16 kernel writes it, and then r is true already)
+        for_each_dst(op, [&](int b, int) { r = r || (b >= 0 && h->bufs[b].p16_ok); });
         op.h16.rerun = r;
-        for (int b : op.extra_out) r = r || h->bufs[b].p16_ok;
-        if (r) {
-            for (int k = 0; k < 2; ++k)
-                if (op.out_buf[k] >= 0) dirty[op.out_buf[k]] = 1;
-            for (int b : op.extra_out) dirty[b] = 1;
-        }
+        if (r) for_each_dst(op, [&](int b, int) { if (b >= 0) dirty[b] = 1; });
     }
 }
 

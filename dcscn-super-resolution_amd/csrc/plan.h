@@ -27,6 +27,11 @@ inline int pad16(int c) { return (c + 15) & ~15; }
 
 enum { EXT_X = -1, EXT_X2 = -2, EXT_Y = -3 };
 enum OpKind { OP_CONV = 0, OP_CIN1 = 1, OP_DW = 2, OP_COUT1 = 3, OP_STREAM = 4, OP_TAIL = 5, OP_STREAM3 = 6, OP_FOLDX = 7 };
+// the kernel a launch runs on (exec.hip: op_kernel decides, launch_op obeys, dcscn_op_info_get reports kernel_name of it);
+// K_LAYER_BY_LAYER = a streamed / folded launch without its split16 kernel: the launches in Op::fused run in its place
+enum Kernel { K_CONV_IGEMM, K_CONV_WINO2, K_CONV_NIN, K_CONV_NIN_H, K_CONV5_H, K_CONV3_H8, K_CONV3_H, K_CONV_CIN1, K_CONV_COUT1, K_DEPTHWISE,
+              K_FEAT_STREAM, K_TAIL_STREAM, K_FEAT3_STREAM, K_LAYER_BY_LAYER };
+constexpr int kNoSplit = 1 << 30;   // Op::split / ConvArgs::split of a launch with ONE destination
 
 struct TensorSpec {
     std::string name;
@@ -46,6 +51,15 @@ struct WsBuf {
     long long plane = 0;  // bytes between chunk planes in the current carve
     size_t bytes = 0;     // bytes of the tensor in the current carve
 };
+
+// THE size of a workspace tensor of npix pixels (ensure_workspace carves it, on 256-byte granules; run_forward sizes a pass by it).
+// A P16 tensor (p16.hpp) is never smaller than its float32 form: the float32 plan of a flagged image reuses the bytes, and its last
+// chunk's record is padded to whole 32-byte octet pairs, so a tensor whose stride is 4 mod 8 is larger than its float32 form.
+inline size_t ws_tensor_bytes(const WsBuf& b, long long npix, bool p16) {
+    const size_t bytes = (size_t)npix * b.stride * sizeof(float);
+    return p16 && b.p16_ok && b.stride > 0 ? std::max(bytes, (size_t)p16_tensor_bytes(npix, b.octs)) : bytes;
+}
+inline size_t ws_granules(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // one source block of a launch's filter matrix: conv channels [dst, dst + cout) come from `w`
 struct ColSeg {
@@ -83,7 +97,7 @@ struct Op {
                                     // OP_FOLDX (fold_whole_tail): fold_s = the net's scale; `fused` = the launches it replaces (the float32 plan, split16 = 0)
     // output
     int out_buf[2] = {EXT_Y, EXT_Y}, out_off[2] = {0, 0}, out_width[2] = {0, 0};
-    int split = 1 << 30;
+    int split = kNoSplit;           // conv channels [split, ..) go to the second destination (has_second_dst)
     int ps = 1, ps_c = 0;
     bool residual = false;
     bool vec4 = true;
@@ -129,6 +143,16 @@ struct Op {
     } h16;
 };
 
+// Which tensors a launch writes: out_buf[0], out_buf[1] when conv channels are split over two destinations, and extra_out.
+// f(buffer, k): k = the destination's index in out_buf / out_off / out_width (0 for extra_out); buffer may be EXT_Y.
+inline bool has_second_dst(const Op& op) { return op.split < (1 << 29); }
+template <class F>
+inline void for_each_dst(const Op& op, F&& f) {
+    f(op.out_buf[0], 0);
+    if (has_second_dst(op)) f(op.out_buf[1], 1);
+    for (int b : op.extra_out) f(b, 0);
+}
+
 }  // namespace dcscn_impl
 
 using namespace dcscn_impl;
@@ -153,7 +177,7 @@ struct dcscn_ctx {
     int lay_n = 0, lay_h = 0, lay_w = 0;     // shape the current carve was made for
     // host-path staging
     float* io_x = nullptr; float* io_x2 = nullptr; float* io_y = nullptr;
-    size_t io_x_cap = 0, io_y_cap = 0;
+    size_t io_x_cap = 0, io_x2_cap = 0, io_y_cap = 0;
     // bicubic resize (resample.hip): Pillow coefficient tables per (in, out) size, and the intermediate image; d_k8 = the
     // 8-bit fixed-point form of d_kk (train_data.hip, made on first use)
     struct ResampleTable { int ksize = 0; int* d_bounds = nullptr; double* d_kk = nullptr; int* d_k8 = nullptr; };
@@ -168,14 +192,13 @@ struct dcscn_ctx {
     size_t col_rgb_cap = 0, col_d_cap = 0, col_d2_cap = 0, col_y32_cap = 0;
     // spatial tiling of images larger than one pass (run_tiled): gathered tile batch
     float* tile_x = nullptr; float* tile_x2 = nullptr; float* tile_y = nullptr;
-    size_t tile_x_cap = 0, tile_y_cap = 0;
+    size_t tile_x_cap = 0, tile_x2_cap = 0, tile_y_cap = 0;
     std::vector<void*> device_allocs;
 
     // LR pixels per pass through the layer chain.  Big passes keep >= ~10 rounds of workgroups per
     // launch on the 256 CUs (a 128-patch pass left a 10-25 % tail); bounded by workspace_budget.
     int64_t sub_batch_pixels = 4 << 20;
     int64_t workspace_budget = (int64_t)48 << 30;   // clamped to a share of the free device memory in dcscn_create
-    bool budget_user_set = false;
     hipEvent_t done_ev = nullptr;            // recorded behind the last forward, on the stream it ran on
     std::vector<hipEvent_t> host_ev;         // dcscn_forward: one per chunk of the host-buffer pipeline
     hipStream_t last_stream = nullptr;
@@ -231,7 +254,6 @@ struct dcscn_ctx {
     size_t ev_used = 0;                      // events recorded since the last dcscn_get_profile
     std::vector<int> ev_op;                  // launch index of each recorded pair (ops.size() = the float32 plan behind a pass)
     int ev_forwards = 0;                     // forwards recorded since the last dcscn_get_profile
-    std::vector<double> prof_ms;
     std::vector<void*> pack_allocs;          // device images finalize_op made (freed and rebuilt when training changed the variables)
     dcscn_impl::TrainState* train = nullptr;      // train.hip: the training plan, variables and slots (dcscn_train_begin)
     dcscn_impl::TrainBatches* batches = nullptr;  // train_data.hip: device-resident training images and the batch planes
@@ -255,17 +277,14 @@ inline float* buf_ptr(dcscn_ctx* h, int id) { return reinterpret_cast<float*>(st
 
 // graph.hip
 void filter_schedule(int layers, int filters, int min_filters, double gamma, std::vector<int>& out);
-int new_buf(dcscn_ctx* h, int stride, int res);
 int kernel_act(int activator, float* const_alpha);
 int build_graph(dcscn_ctx* h);
-int op_tiles16(const Op& op);
 bool nin_eligible(const dcscn_ctx* h, const Op& op);
 bool wino_eligible(const dcscn_ctx* h, const Op& op);
 bool h16_direct_eligible(const dcscn_ctx* h, const Op& op);
 bool fold_linear_tail(dcscn_ctx* h);
 bool fold_whole_tail(dcscn_ctx* h);
 int stream_chunk_channel(int quads, int ch, int q, int s);
-bool stream_conv_supported(int in_quads, int out_tiles);
 void fuse_feat_stream(dcscn_ctx* h);
 void fuse_tail_stream(dcscn_ctx* h);
 void fuse_feat3_stream(dcscn_ctx* h);
@@ -290,17 +309,26 @@ int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, d
                        hipStream_t stream);
 void train_batches_free(dcscn_ctx* h);
 // exec.hip
-int ensure_workspace(dcscn_ctx* h, int nb, int H, int W, hipStream_t stream);
-// redo = false: the launch of the pass (split16 kernels where the handle's options allow); true: the op's float32 launch gated by the
-// pass's redo flags -- only the images a split16 launch flagged are computed (exec.hip: run_forward)
-int launch_op(dcscn_ctx* h, const Op& op, int nb, int H, int W, const float* x, const float* x2, float* y, hipStream_t stream, bool redo = false);
 bool op_on_split16(const dcscn_ctx* h, const Op& op);
-bool op_takes_h8(const dcscn_ctx* h, const Op& op);
-int halo_lr_pixels(const dcscn_ctx* h);
+Kernel op_kernel(const dcscn_ctx* h, const Op& op, bool redo = false);
+const char* kernel_name(Kernel k);
 int run_forward(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, int H, int W, hipStream_t stream);
-int run_tiled(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, int H, int W, int64_t pass_pixels, hipStream_t stream);
+int forward_done(dcscn_ctx* h, hipStream_t stream);   // records done_ev behind the handle's last work on `stream`
 int resample_table(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::ResampleTable** out);
-int grow(dcscn_ctx* h, float** p, size_t* cap, size_t floats, hipStream_t stream);
+// A device buffer that only grows: synchronise `stream` (the buffer's users), free, allocate `count` elements, record the capacity.
+// A failed allocation is DCSCN_ERR_NOMEM, or `nomem_code` for the entry points that have always reported it as DCSCN_ERR_HIP.
+template <class T>
+int grow(dcscn_ctx* h, T** p, size_t* cap, size_t count, hipStream_t stream, int nomem_code = DCSCN_ERR_NOMEM) {
+    if (count <= *cap) return DCSCN_OK;
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    if (*p) HIP_TRY(h, hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
+    if (e != hipSuccess) return fail(h, nomem_code, "buffer of %zu bytes: %s", count * sizeof(T), hipGetErrorString(e));
+    *cap = count;
+    return DCSCN_OK;
+}
 int resize_device(dcscn_ctx* h, const float* in, float* out, int n, int H, int W, int OH, int OW, hipStream_t stream);
 
 }  // namespace dcscn_impl

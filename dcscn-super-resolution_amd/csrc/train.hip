@@ -385,6 +385,9 @@ struct TLayer {
     float* z = nullptr;            // pre-activation, dense [P res^2, cout]
 };
 
+// the variables the l2 term sums over: the filters, not biases or prelu slopes
+static bool is_conv_w(const std::string& name) { return name.size() >= 7 && name.compare(name.size() - 7, 7, "/conv_W") == 0; }
+
 static constexpr int kLossBlocks = 256, kNormBlocks = 256, kW2Blocks = 32;   // (kW2Blocks: per conv_W tensor, for the l2 term)
 
 struct TrainState {
@@ -655,8 +658,7 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
     double* w2p = t->dpart + 2 * kLossBlocks;
     int slot = 0;
     for (size_t i = 0; i < h->tensors.size(); ++i) {
-        const std::string& nm = h->tensors[i].name;
-        if (nm.size() < 7 || nm.compare(nm.size() - 7, 7, "/conv_W") != 0) continue;
+        if (!is_conv_w(h->tensors[i].name)) continue;
         const int64_t c = (int64_t)h->tensors[i].data.size();
         KTRY(h, hipLaunchKernelGGL(tsumsq, dim3(kW2Blocks), dim3(256), 0, st, (const float*)(t->d_w + t->off[i]), c, (c + kW2Blocks - 1) / kW2Blocks,
                                    w2p + slot));
@@ -688,6 +690,14 @@ static int check_step(dcscn_ctx* h, const void* x, const void* x2, const void* y
     return DCSCN_OK;
 }
 
+// the four doubles of a step's stats (tstats) to the caller, who asked for them: synchronises `st`; stats == nullptr: nothing, the step stays enqueued
+static int read_stats(dcscn_ctx* h, TrainState* t, double* stats, hipStream_t st) {
+    if (!stats) return DCSCN_OK;
+    HIP_TRY(h, hipMemcpyAsync(stats, t->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return DCSCN_OK;
+}
+
 // steps in host memory: upload, step, read the stats back
 static int host_step(dcscn_ctx* h, const float* x, const float* x2, const float* y, int n, int H, int W, double lr, uint64_t key, double* stats, bool update) {
     int rc = check_step(h, x, x2, y, n, H, W);
@@ -703,11 +713,8 @@ static int host_step(dcscn_ctx* h, const float* x, const float* x2, const float*
     HIP_TRY(h, hipMemcpyAsync(t->io_y, y, hr_b, hipMemcpyHostToDevice, st));
     if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, key, st))) return rc;
     if (update && (rc = apply_update(h, t, lr, st))) return rc;
-    double buf[4];
-    HIP_TRY(h, hipMemcpyAsync(buf, t->d_stats, sizeof buf, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (stats) memcpy(stats, buf, sizeof buf);
-    return DCSCN_OK;
+    if (!stats) HIP_TRY(h, hipStreamSynchronize(st));     // (the uploads read the caller's buffers: done with them on return, stats or not)
+    return read_stats(h, t, stats, st);
 }
 
 void train_free(dcscn_ctx* h) {
@@ -771,7 +778,7 @@ int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc) {
     for (const TensorSpec& ts : h->tensors) {
         t->off.push_back(t->count);
         t->count += (int64_t)ts.data.size();
-        if (ts.name.size() >= 7 && ts.name.compare(ts.name.size() - 7, 7, "/conv_W") == 0) t->w2_blocks += kW2Blocks;
+        if (is_conv_w(ts.name)) t->w2_blocks += kW2Blocks;
     }
     std::vector<float> flat((size_t)t->count);
     for (size_t i = 0; i < h->tensors.size(); ++i) std::copy(h->tensors[i].data.begin(), h->tensors[i].data.end(), flat.begin() + t->off[i]);
@@ -813,10 +820,7 @@ int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, con
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     if ((rc = run_gradients(h, t, x, x2, y_true, dropout_key, st))) return rc;
     if ((rc = apply_update(h, t, lr, st))) return rc;
-    if (stats) {
-        HIP_TRY(h, hipMemcpyAsync(stats, t->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-    }
+    if ((rc = read_stats(h, t, stats, st))) return rc;
     if (st != h->stream) {   // later host-buffer steps and forwards run on the handle's stream
         hipEvent_t ev;
         HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -839,11 +843,7 @@ int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, 
     if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;   // train_data.hip
     if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st))) return rc;
     if ((rc = apply_update(h, t, lr, st))) return rc;
-    if (stats) {
-        HIP_TRY(h, hipMemcpyAsync(stats, t->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(h, hipStreamSynchronize(st));
-    }
-    return DCSCN_OK;
+    return read_stats(h, t, stats, st);
 }
 
 // "<var>", "<var>/grad", "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power"
