@@ -640,11 +640,12 @@ static int download_sr(dcscn_ctx* h, size_t hr, int n_ensemble, double* y) {
     return DCSCN_OK;
 }
 
-int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, double* true_y, float* lr, double* y) {
-    if (!h) return DCSCN_ERR_INVALID_ARG;
-    if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_evaluate_rgb before dcscn_finalize");
+// The pipeline of dcscn_evaluate_rgb up to the result on the device: true Y float64 in col_d, LR in io_x, its bicubic in io_x2, the
+// output in io_y (n_ensemble == 1) or ens_out; enqueued only.  `what` names the entry point in the messages.
+static int evaluate_rgb_on_device(dcscn_ctx* h, const uint8_t* rgb, int height, int width, int n_ensemble, const char* what) {
+    if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "%s before dcscn_finalize", what);
     if (int rc_ = train_sync_inference(h)) return rc_;
-    if (!rgb || !y) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_evaluate_rgb: null pointer");
+    if (!rgb) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: null pointer", what);
     if (n_ensemble < 1 || n_ensemble > 8) return fail(h, DCSCN_ERR_INVALID_ARG, "n_ensemble %d outside [1, 8]", n_ensemble);
     const int s = h->cfg.scale;
     if (height <= 0 || width <= 0 || height % s || width % s)
@@ -662,11 +663,123 @@ int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width
     HIP_TRY(h, rgb_to_y_launch(reinterpret_cast<const uint8_t*>(h->col_rgb), reinterpret_cast<double*>(h->col_d), h->col_y32, (long long)hr, h->stream));
     rc = resize_device(h, h->col_y32, h->io_x, 1, height, width, lh, lw, h->stream);                    // loader.py:64-65
     if (!rc) rc = sr_from_lr_on_device(h, lh, lw, n_ensemble);
+    return rc;
+}
+
+int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, double* true_y, float* lr, double* y) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = evaluate_rgb_on_device(h, y ? rgb : nullptr, height, width, n_ensemble, "dcscn_evaluate_rgb");
+    const size_t hr = (size_t)height * width, lrn = hr / ((size_t)h->cfg.scale * h->cfg.scale);
     if (!rc) rc = download_sr(h, hr, n_ensemble, y);
     if (rc) return rc;
     if (true_y) HIP_TRY(h, hipMemcpy(true_y, h->col_d, hr * sizeof(double), hipMemcpyDeviceToHost));
     if (lr) HIP_TRY(h, hipMemcpy(lr, h->io_x, lrn * sizeof(float), hipMemcpyDeviceToHost));
     return DCSCN_OK;
+}
+
+// ---- PSNR / SSIM on the device (metrics.hip; utilty.py:509-536) -------------------------------------------------------
+
+// The window of scipy's gaussian_filter1d(sigma 1.5, truncate 3.5): exp(-0.5 / sigma^2 * x^2) / sum for x = -5 .. 5, float64.
+// The sum is taken in numpy's order for 11 elements (eight lanes paired, then the last three), so the weights have numpy's bits.
+static const MetricWeights& metric_weights() {
+    static const MetricWeights wt = [] {
+        MetricWeights m;
+        const double sigma2 = 1.5 * 1.5;
+        for (int k = 0; k < kMetricTaps; ++k) {
+            const double x = (double)(k - kMetricTaps / 2);
+            m.w[k] = exp(-0.5 / sigma2 * (x * x));
+        }
+        double sum = ((m.w[0] + m.w[1]) + (m.w[2] + m.w[3])) + ((m.w[4] + m.w[5]) + (m.w[6] + m.w[7]));
+        for (int k = 8; k < kMetricTaps; ++k) sum += m.w[k];
+        for (int k = 0; k < kMetricTaps; ++k) m.w[k] = m.w[k] / sum;
+        return m;
+    }();
+    return wt;
+}
+
+// the shaved size of a [height, width] image, or the host's refusal (imaging._ssim_last_axis_channels: ValueError)
+static int metric_shape(dcscn_ctx* h, int height, int width, int border, const char* what, int* sh, int* sw) {
+    if (height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: bad shape h=%d w=%d", what, height, width);
+    if (border < 0) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: negative border_size %d (win_size cannot be placed)", what, border);
+    *sh = height - 2 * border;
+    *sw = width - 2 * border;
+    if (*sh < kMetricTaps || *sw < 1)
+        return fail(h, DCSCN_ERR_INVALID_ARG, "%s: win_size exceeds image extent (%d x %d after shaving %d: needs %d rows and 1 column)", what,
+                    *sh, *sw, border, kMetricTaps);
+    return DCSCN_OK;
+}
+
+static int metric_buffers(dcscn_ctx* h, int sh, int sw) {
+    return grow(h, &h->met_buf, &h->met_buf_cap, (size_t)8 + 2 * (size_t)metric_segments(sh) * sw, h->stream);
+}
+
+// enqueue the two launches for one image pair into result slot 0 or 1 of met_buf
+static int metric_enqueue(dcscn_ctx* h, int slot, const double* a64, const float* a32, const double* b64, const float* b32, int width, int border,
+                          int sh, int sw) {
+    double* part_s = h->met_buf + 8;
+    long long* part_e = reinterpret_cast<long long*>(part_s + (size_t)metric_segments(sh) * sw);
+    HIP_TRY(h, metrics_launch(a64, a32, b64, b32, width, border, sh, sw, metric_weights(), part_s, part_e,
+                              reinterpret_cast<long long*>(h->met_buf) + 4 * slot, h->stream));
+    return DCSCN_OK;
+}
+
+// synchronise, fetch the result slots and form the PSNR as the host does: 10 log10(255^2 / (sum / n)), +inf for an exact match
+static int metric_download(dcscn_ctx* h, dcscn_metrics* first, dcscn_metrics* second) {
+    long long words[8];
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(words, h->met_buf, sizeof words, hipMemcpyDeviceToHost));
+    dcscn_metrics* outs[2] = {first, second};
+    for (int i = 0; i < 2; ++i) {
+        if (!outs[i]) continue;
+        dcscn_metrics& m = *outs[i];
+        m.sq_err_sum = words[4 * i];
+        m.n_pixels = words[4 * i + 1];
+        memcpy(&m.ssim, &words[4 * i + 2], sizeof(double));
+        const double err = (double)m.sq_err_sum / (double)m.n_pixels;
+        m.psnr = m.sq_err_sum == 0 ? (double)INFINITY : 10.0 * log10((255.0 * 255.0) / err);
+    }
+    return DCSCN_OK;
+}
+
+int dcscn_psnr_ssim(dcscn_handle h, const double* a, const double* b, int height, int width, int border_size, dcscn_metrics* out) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!a || !b || !out) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_psnr_ssim: null pointer");
+    int sh, sw;
+    int rc = metric_shape(h, height, width, border_size, "dcscn_psnr_ssim", &sh, &sw);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)height * width;
+    rc = grow(h, &h->col_d, &h->col_d_cap, 2 * n, h->stream);
+    if (!rc) rc = grow(h, &h->col_d2, &h->col_d2_cap, 2 * n, h->stream);
+    if (!rc) rc = metric_buffers(h, sh, sw);
+    if (rc) return rc;
+    const double* da = reinterpret_cast<const double*>(h->col_d);
+    const double* db = reinterpret_cast<const double*>(h->col_d2);
+    HIP_TRY(h, hipMemcpy(h->col_d, a, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->col_d2, b, n * sizeof(double), hipMemcpyHostToDevice));
+    rc = metric_enqueue(h, 0, da, nullptr, db, nullptr, width, border_size, sh, sw);
+    if (!rc) rc = metric_download(h, out, nullptr);
+    return rc;
+}
+
+int dcscn_evaluate_rgb_metrics(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, int border_size, dcscn_metrics* model,
+                               dcscn_metrics* bicubic, double* y) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_evaluate_rgb_metrics before dcscn_finalize");
+    if (!rgb || !model) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_evaluate_rgb_metrics: null pointer");
+    int sh, sw;
+    int rc = metric_shape(h, height, width, border_size, "dcscn_evaluate_rgb_metrics", &sh, &sw);
+    if (!rc) rc = evaluate_rgb_on_device(h, rgb, height, width, n_ensemble, "dcscn_evaluate_rgb_metrics");
+    if (!rc) rc = metric_buffers(h, sh, sw);
+    if (rc) return rc;
+    const double* true_y = reinterpret_cast<const double*>(h->col_d);
+    // do_for_evaluate: compute_psnr_and_ssim(true_y, output); evaluate_bicubic: compute_psnr_and_ssim(true_y, bicubic of LR)
+    rc = metric_enqueue(h, 0, true_y, nullptr, n_ensemble > 1 ? reinterpret_cast<const double*>(h->ens_out) : nullptr,
+                        n_ensemble > 1 ? nullptr : h->io_y, width, border_size, sh, sw);
+    if (!rc && bicubic) rc = metric_enqueue(h, 1, true_y, nullptr, nullptr, h->io_x2, width, border_size, sh, sw);
+    if (!rc) rc = metric_download(h, model, bicubic);
+    if (!rc && y) rc = download_sr(h, (size_t)height * width, n_ensemble, y);
+    return rc;
 }
 
 int dcscn_sr_rgb(dcscn_handle h, const uint8_t* rgb, const uint8_t* rgb_upscaled, int height, int width, int n_ensemble, double* y, double* rgb_out) {
@@ -781,6 +894,7 @@ int dcscn_destroy(dcscn_handle h) {
     for (float* p : {h->io_x, h->io_x2, h->io_y, h->tile_x, h->tile_x2, h->tile_y, h->rs_tmp, h->rs_in, h->rs_out, h->ens_x, h->ens_x2, h->ens_y, h->ens_out, h->col_rgb, h->col_d,
                      h->col_d2, h->col_y32})
         if (p) (void)hipFree(p);
+    if (h->met_buf) (void)hipFree(h->met_buf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return DCSCN_OK;

@@ -299,6 +299,15 @@ hipError_t rgb_to_ycbcr_launch(const uint8_t* rgb, double* out, long long n, hip
 hipError_t y_cbcr_to_rgb_launch(const double* y64, const float* y32, const double* cbcr, const uint8_t* rgb8, double* out, long long n,
                                 hipStream_t stream);
 
+// PSNR / SSIM of two single-channel images (metrics.hip): trimmed like a saved file, shaved by `border`; h, w = the shaved size
+// (h >= kMetricTaps, w >= 1), stride = the row length of both images; each image is float64 or, with its *32 pointer set, float32.
+// part_s / part_e: metric_segments(h) * w elements each; out: 3 x int64 = {squared-error sum, pixels, bits of the SSIM double}.
+constexpr int kMetricTaps = 11;
+struct MetricWeights { double w[kMetricTaps]; };       // the normalised Gaussian window, made on the host
+int metric_segments(int h);
+hipError_t metrics_launch(const double* a64, const float* a32, const double* b64, const float* b32, int stride, int border, int h, int w,
+                          const MetricWeights& wt, double* part_s, long long* part_e, long long* out, hipStream_t stream);
+
 // Pillow-compatible bicubic resize of 1-channel float images (resample.hip)
 int resample_coeffs(int in_size, int out_size, std::vector<int>* bounds, std::vector<double>* kk);   // returns ksize
 hipError_t resample_h_launch(const float* in, float* out, const int* bounds, const double* kk, int ksize,

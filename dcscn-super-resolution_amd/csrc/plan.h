@@ -190,6 +190,8 @@ struct dcscn_ctx {
     // colour path (color.hip): uint8 RGB in, float64 planes, float32 Y; capacities in floats
     float* col_rgb = nullptr; float* col_d = nullptr; float* col_d2 = nullptr; float* col_y32 = nullptr;
     size_t col_rgb_cap = 0, col_d_cap = 0, col_d2_cap = 0, col_y32_cap = 0;
+    // metrics (metrics.hip): 2 x 4 result words (model, bicubic), then the per-segment partials of one image pair; in doubles
+    double* met_buf = nullptr; size_t met_buf_cap = 0;
     // spatial tiling of images larger than one pass (run_tiled): gathered tile batch
     float* tile_x = nullptr; float* tile_x2 = nullptr; float* tile_y = nullptr;
     size_t tile_x_cap = 0, tile_x2_cap = 0, tile_y_cap = 0;

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 MAX_NAME = 128
 
 ACTIVATORS = {None: 0, "": 0, "none": 0, "prelu": 1, "relu": 2, "leaky_relu": 3, "sigmoid": 4, "tanh": 5, "selu": 6}
@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "dcscn_convert_y_and_cbcr_to_rgb", "dcscn_evaluate_rgb", "dcscn_sr_rgb",
     "dcscn_train_begin", "dcscn_train_step", "dcscn_train_step_device", "dcscn_train_gradients", "dcscn_get_tensor",
     "dcscn_set_train_tensor", "dcscn_train_add_image", "dcscn_train_build_batch", "dcscn_train_step_patches",
+    "dcscn_psnr_ssim", "dcscn_evaluate_rgb_metrics",
 )
 
 # dcscn_optimizer; the names of helper/args.py --optimizer
@@ -117,6 +118,16 @@ class OpInfo(ctypes.Structure):
     ]
 
 
+class Metrics(ctypes.Structure):
+    """dcscn_metrics: PSNR / SSIM of one image pair and the exact integers the PSNR is formed from."""
+    _fields_ = [
+        ("psnr", ctypes.c_double),
+        ("ssim", ctypes.c_double),
+        ("sq_err_sum", ctypes.c_int64),
+        ("n_pixels", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -171,6 +182,8 @@ def load_library():
     lib.dcscn_convert_y_and_cbcr_to_rgb.argtypes = [vp, dp, dp, dp, c.c_int64]
     lib.dcscn_evaluate_rgb.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, dp, fp, dp]
     lib.dcscn_sr_rgb.argtypes = [vp, u8p, u8p, c.c_int, c.c_int, c.c_int, dp, dp]
+    lib.dcscn_psnr_ssim.argtypes = [vp, dp, dp, c.c_int, c.c_int, c.c_int, c.POINTER(Metrics)]
+    lib.dcscn_evaluate_rgb_metrics.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(Metrics), c.POINTER(Metrics), dp]
     lib.dcscn_synchronize.argtypes = [vp]
     lib.dcscn_workspace_bytes.restype = c.c_int64
     lib.dcscn_last_error.argtypes = [vp]
@@ -608,6 +621,45 @@ class Engine:
         if n_ensemble <= 1:
             y = y.astype(np.float32)
         return (true_y, y, lr) if want_inputs else (true_y, y)
+
+    # ---- metrics (helper/utilty.py:509-536 on the device: csrc/metrics.hip) ----
+    def psnr_ssim(self, a, b, border_size=0, full=False):
+        """compute_psnr_and_ssim(a, b, border_size) for two single-channel images [H, W] or [H, W, 1] of any real dtype:
+        (psnr, ssim), or None when the shapes differ, like the host function; ``full``: the whole Metrics struct instead.
+        An image with fewer than 11 rows left after shaving is an EngineError (INVALID_ARG, "win_size ...")."""
+        a, b = np.asarray(a), np.asarray(b)
+        if a.ndim == 2:
+            a = a.reshape(a.shape[0], a.shape[1], 1)
+        if b.ndim == 2:
+            b = b.reshape(b.shape[0], b.shape[1], 1)
+        if a.shape != b.shape:
+            return None
+        if a.ndim != 3 or a.shape[2] != 1:
+            raise EngineError(1, "psnr_ssim expects single-channel images, got shape %s" % (a.shape,))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        dp = ctypes.POINTER(ctypes.c_double)
+        out = Metrics()
+        self._check(self._lib.dcscn_psnr_ssim(self._h, a.ctypes.data_as(dp), b.ctypes.data_as(dp), a.shape[0], a.shape[1], int(border_size),
+                                              ctypes.byref(out)))
+        return out if full else (out.psnr, out.ssim)
+
+    def evaluate_rgb_metrics(self, true_image, n_ensemble=1, border_size=0, want_bicubic=False, want_output=False, full=False):
+        """evaluate_rgb's pipeline with PSNR / SSIM taken on the device: returns ((psnr, ssim) of the output against the true Y,
+        (psnr, ssim) of the bicubic of LR against the true Y or None, the output like evaluate_rgb's or None).  Without
+        want_output no image comes back to the host.  ``full``: Metrics structs in place of the pairs."""
+        a = self._rgb8(true_image)
+        hh, ww = a.shape[:2]
+        model = Metrics()
+        bicubic = Metrics() if want_bicubic else None
+        y = np.empty((hh, ww, 1), np.float64) if want_output else None
+        self._check(self._lib.dcscn_evaluate_rgb_metrics(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), hh, ww, max(1, int(n_ensemble)),
+                                                         int(border_size), ctypes.byref(model), ctypes.byref(bicubic) if want_bicubic else None,
+                                                         y.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if want_output else None))
+        if want_output and n_ensemble <= 1:
+            y = y.astype(np.float32)
+        pair = (lambda m: m) if full else (lambda m: (m.psnr, m.ssim))
+        return pair(model), pair(bicubic) if want_bicubic else None, y
 
     def sr_rgb(self, image, upscaled_image, n_ensemble=1):
         """do_for_file's colour branch: (super-resolved Y [s*h, s*w, 1], RGB float64 [s*h, s*w, 3])."""

@@ -88,6 +88,8 @@ class SuperResolution:
         self.psnr_calc_border_size = flags.psnr_calc_border_size
         if self.psnr_calc_border_size < 0:
             self.psnr_calc_border_size = self.scale
+        # extension: PSNR / SSIM of evaluated images on the device (csrc/metrics.hip) instead of numpy / scipy; off = the host code
+        self.device_metrics = bool(getattr(flags, "device_metrics", False))
 
         # training parameters (DCSCN.py:50-93)
         fget = lambda k, d: getattr(flags, k, d)
@@ -595,6 +597,27 @@ class SuperResolution:
                 and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3
                 and self.ensemble_group is None)              # the all-device pipeline runs the whole ensemble on this rank
 
+    def _metrics(self, image1, image2):
+        """compute_psnr_and_ssim at the model's border: on the host, or with device_metrics on the device (dcscn_psnr_ssim)."""
+        if not self.device_metrics:
+            return util.compute_psnr_and_ssim(image1, image2, border_size=self.psnr_calc_border_size)
+        return self._on_device_metrics(self._ready_engine().psnr_ssim, image1, image2, border_size=self.psnr_calc_border_size)
+
+    @staticmethod
+    def _on_device_metrics(call, *args, **kwargs):
+        """The engine's refusal of an image too small for the 11-row SSIM window, as the ValueError the host code raises."""
+        try:
+            return call(*args, **kwargs)
+        except engine.EngineError as e:
+            if e.status == 1 and "win_size" in e.message:
+                raise ValueError("win_size exceeds image extent")
+            raise
+
+    def _evaluate_rgb_metrics(self, true_image, n_ensemble, want_bicubic=False):
+        """(model pair, bicubic pair or None) of an RGB file wholly on the device: no image is downloaded (dcscn_evaluate_rgb_metrics)."""
+        return self._on_device_metrics(self._ready_engine().evaluate_rgb_metrics, true_image, n_ensemble,
+                                       border_size=self.psnr_calc_border_size, want_bicubic=want_bicubic)[:2]
+
     def _evaluation_inputs(self, file_path):
         """(true image aligned, true Y or grey, LR input, bicubic of LR) -- DCSCN.py:674-683."""
         true_image = util.set_image_alignment(util.load_image(file_path, print_console=False), self.scale)
@@ -613,17 +636,20 @@ class SuperResolution:
     def do_for_evaluate(self, file_path, print_console=False):
         """(psnr, ssim) of one file (DCSCN.py:672-703)."""
         true_image = util.set_image_alignment(util.load_image(file_path, print_console=False), self.scale)
-        if self._device_colour_path(true_image):
-            # one upload: Y conversion, both bicubic resizes, the (ensemble of) forward pass on the device (dcscn_evaluate_rgb)
-            true_y, output = self._ready_engine().evaluate_rgb(true_image, self.self_ensemble)
+        if self._device_colour_path(true_image) and self.device_metrics:
+            psnr, ssim = self._evaluate_rgb_metrics(true_image, self.self_ensemble)[0]     # ... and the metrics: nothing comes back but them
         else:
-            true_image, true_y, input_image, bicubic = self._evaluation_inputs(file_path)
-            if true_y is None:
-                return None, None
-            output = self.do(input_image, bicubic)
-            if output is None:
-                return 0.0, 0.0                               # split ensemble, not rank 0: the values are rank 0's (evaluate.py logs there)
-        psnr, ssim = util.compute_psnr_and_ssim(true_y, output, border_size=self.psnr_calc_border_size)
+            if self._device_colour_path(true_image):
+                # one upload: Y conversion, both bicubic resizes, the (ensemble of) forward pass on the device (dcscn_evaluate_rgb)
+                true_y, output = self._ready_engine().evaluate_rgb(true_image, self.self_ensemble)
+            else:
+                true_image, true_y, input_image, bicubic = self._evaluation_inputs(file_path)
+                if true_y is None:
+                    return None, None
+                output = self.do(input_image, bicubic)
+                if output is None:
+                    return 0.0, 0.0                           # split ensemble, not rank 0: the values are rank 0's (evaluate.py logs there)
+            psnr, ssim = self._metrics(true_y, output)
         if print_console:
             print("[%s] PSNR:%f, SSIM:%f" % (file_path, psnr, ssim))
         return psnr, ssim
@@ -635,9 +661,11 @@ class SuperResolution:
         the metric code (utilty.py:509-536, numpy / scipy: it releases the GIL) of the PREVIOUS ones on two more, and this thread
         alone drives the engine (the handle is not thread safe) in file order.  Every value is computed by the same functions on
         the same data as in do_for_evaluate: the results are identical.  `seconds` = wall clock of the whole call / number of files
-        (what a caller waits per file; the reference's figure is the serial time of each file)."""
+        (what a caller waits per file; the reference's figure is the serial time of each file).
+        With device_metrics the metric stage is part of the device stage and its two threads are not started."""
         import time
         from concurrent.futures import ThreadPoolExecutor
+        from contextlib import nullcontext
         n = len(file_paths)
         if n == 0:
             return []
@@ -646,10 +674,19 @@ class SuperResolution:
         def decode(path):
             return util.set_image_alignment(util.load_image(path, print_console=False), self.scale)
 
-        def metrics(true_y, output):
-            return util.compute_psnr_and_ssim(true_y, output, border_size=self.psnr_calc_border_size)
+        class _Done:                                          # a value already computed, with a future's result()
+            def __init__(self, value):
+                self.value = value
 
-        with ThreadPoolExecutor(max_workers=1) as dec, ThreadPoolExecutor(max_workers=2) as met:
+            def result(self):
+                return self.value
+
+        def metrics(true_y, output):
+            if self.device_metrics:                           # on this thread: the engine computes them (the handle is not thread safe)
+                return _Done(self._metrics(true_y, output))
+            return met.submit(self._metrics, true_y, output)
+
+        with ThreadPoolExecutor(max_workers=1) as dec, (nullcontext() if self.device_metrics else ThreadPoolExecutor(max_workers=2)) as met:
             ahead = 2
             pending = {i: dec.submit(decode, file_paths[i]) for i in range(min(ahead, n))}
             results = []
@@ -657,12 +694,15 @@ class SuperResolution:
                 true_image = pending.pop(i).result()
                 if i + ahead < n:
                     pending[i + ahead] = dec.submit(decode, file_paths[i + ahead])
+                if self._device_colour_path(true_image) and self.device_metrics:
+                    results.append(_Done(self._evaluate_rgb_metrics(true_image, self.self_ensemble)[0]))
+                    continue
                 if self._device_colour_path(true_image):
                     true_y, output = self._ready_engine().evaluate_rgb(true_image, self.self_ensemble)
                 else:
                     true_image, true_y, input_image, bicubic = self._evaluation_inputs(file_paths[i])
                     output = None if true_y is None else self.do(input_image, bicubic)
-                results.append(None if true_y is None else met.submit(metrics, true_y, output))
+                results.append(None if true_y is None else metrics(true_y, output))
             values = [(None, None) if r is None else r.result() for r in results]
         per_file = (time.time() - t0) / n
         if print_console:
@@ -689,8 +729,7 @@ class SuperResolution:
                                                              resampling_method=self.resampling_method)
             true_ycbcr_image = util.convert_rgb_to_ycbcr(true_image)
             output_y_image = self.do(input_y_image, input_bicubic_y_image)
-            psnr, ssim = util.compute_psnr_and_ssim(true_ycbcr_image[:, :, 0:1], output_y_image,
-                                                    border_size=self.psnr_calc_border_size)
+            psnr, ssim = self._metrics(true_ycbcr_image[:, :, 0:1], output_y_image)
             loss_image = util.get_loss_image(true_ycbcr_image[:, :, 0:1], output_y_image,
                                              border_size=self.psnr_calc_border_size)
             output_color_image = util.convert_y_and_cbcr_to_rgb(output_y_image, true_ycbcr_image[:, :, 1:3])
@@ -706,7 +745,7 @@ class SuperResolution:
             input_bicubic_y_image = util.resize_image_by_pil(input_image, self.scale,
                                                              resampling_method=self.resampling_method)
             output_image = self.do(input_image, input_bicubic_y_image)
-            psnr, ssim = util.compute_psnr_and_ssim(true_image, output_image, border_size=self.psnr_calc_border_size)
+            psnr, ssim = self._metrics(true_image, output_image)
             util.save_image(output_directory + file_path, true_image)
             util.save_image(output_directory + filename + "_result" + extension, output_image)
         else:
@@ -718,10 +757,15 @@ class SuperResolution:
 
     def evaluate_bicubic(self, file_path, print_console=False):
         """PSNR / SSIM of plain bicubic upscaling (DCSCN.py:705-725)."""
-        true_image, true_y, input_image, bicubic = self._evaluation_inputs(file_path)
-        if true_y is None:
-            return None, None
-        psnr, ssim = util.compute_psnr_and_ssim(true_y, bicubic, border_size=self.psnr_calc_border_size)
+        true_image = util.set_image_alignment(util.load_image(file_path, print_console=False), self.scale) if self.device_metrics else None
+        if true_image is not None and self._device_colour_path(true_image):
+            # the pipeline's own bicubic of LR against its true Y (one forward pass of ensemble 1 rides along)
+            psnr, ssim = self._evaluate_rgb_metrics(true_image, 1, want_bicubic=True)[1]
+        else:
+            true_image, true_y, input_image, bicubic = self._evaluation_inputs(file_path)
+            if true_y is None:
+                return None, None
+            psnr, ssim = self._metrics(true_y, bicubic)
         if print_console:
             print("PSNR:%f, SSIM:%f" % (psnr, ssim))
         return psnr, ssim

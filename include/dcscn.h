@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DCSCN_ABI_VERSION 3
+#define DCSCN_ABI_VERSION 4
 #define DCSCN_MAX_NAME 128
 
 typedef struct dcscn_ctx* dcscn_handle;
@@ -285,6 +285,31 @@ int dcscn_convert_y_and_cbcr_to_rgb(dcscn_handle h, const double* y, const doubl
  * true_y float64 [height, width] (what the PSNR is measured against) and lr float32 [height/s, width/s]. */
 int dcscn_evaluate_rgb(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble,
                        double* true_y, float* lr, double* y);
+
+/* PSNR and SSIM as evaluate.py reports them (compute_psnr_and_ssim, utilty.py:509-536), computed on the device.  Both images are
+ * trimmed like a saved file (rint, half to even, then clipped to [0, 255]) and shaved by border_size pixels on every side.
+ *   sq_err_sum, n_pixels   exact integers over the shaved pixels; psnr = 10 log10(255^2 / (sq_err_sum / n_pixels)), formed on the
+ *                          host from the two, +inf when sq_err_sum is 0
+ *   ssim                   what the reference's multichannel=True call on 2-D arrays yields: the mean over image columns of a
+ *                          1-D SSIM down each column (11-tap Gaussian window, sigma 1.5, sample covariance), taken over the rows
+ *                          whose window lies inside the shaved image.  float64; two calls give the same bits.
+ * DCSCN_ERR_INVALID_ARG with "win_size" in the message: fewer than 11 rows or no column left after shaving, or a negative
+ * border_size (the reference raises "win_size exceeds image extent").  Pixel values must be finite. */
+typedef struct dcscn_metrics {
+    double  psnr;
+    double  ssim;
+    int64_t sq_err_sum;
+    int64_t n_pixels;
+} dcscn_metrics;   /* 32 bytes */
+
+/* Two single-channel float64 images [height, width] in host memory (synchronous; usable before dcscn_finalize). */
+int dcscn_psnr_ssim(dcscn_handle h, const double* a, const double* b, int height, int width, int border_size, dcscn_metrics* out);
+
+/* dcscn_evaluate_rgb with the metrics taken on the device from the images the pipeline already holds there: `model` = the
+ * network output against the true Y (do_for_evaluate), `bicubic` (optional) = the bicubic of LR against the true Y
+ * (evaluate_bicubic).  y (optional) receives the output like dcscn_evaluate_rgb's; when it is null no image is downloaded. */
+int dcscn_evaluate_rgb_metrics(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, int border_size,
+                               dcscn_metrics* model, dcscn_metrics* bicubic, double* y);
 
 /* do_for_file's colour pipeline (sr.py; DCSCN.py:588-614): rgb uint8 [height, width, 3] is the input image,
  * rgb_upscaled uint8 [s*height, s*width, 3] its Pillow-upscaled copy (the reference builds it on the host for the
