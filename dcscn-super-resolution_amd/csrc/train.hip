@@ -224,27 +224,28 @@ __global__ void tcol_final(const float* part, int cout, int splits, float* grad)
     grad[co] = s;
 }
 
-// forward epilogue of a conv with an activator: h = act(z), then dropout (mask / keep), into a strided slice
+// forward epilogue of a conv with an activator: h = act(z), then dropout (mask / keep), into a strided slice.  idx0 = the index of
+// the batch's first element within the global batch (a shard of a data-parallel step; 0 otherwise): the mask is the whole batch's
 __global__ void tact_fwd(const float* z, int cout, int64_t P, const float* alpha, float calpha, int act, float* h, int h_stride,
-                         uint64_t lkey, uint32_t thresh, float keep, int dropout) {
+                         uint64_t lkey, uint64_t idx0, uint32_t thresh, float keep, int dropout) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= P * cout) return;
     const int64_t p = e / cout;
     const int co = (int)(e - p * cout);
     float v = tact(z[e], alpha ? alpha[co] : calpha, act);
-    if (dropout) v = dropout_keep(lkey, (uint64_t)e, thresh) ? v / keep : 0.0f;
+    if (dropout) v = dropout_keep(lkey, idx0 + (uint64_t)e, thresh) ? v / keep : 0.0f;
     h[p * h_stride + co] = v;
 }
 
 // backward through dropout and the activator: dA = dh * mask / keep; dz = dA * act'(z); at = dA * min(z, 0) (PReLU alpha term)
 __global__ void tact_bwd(const float* dh, int dh_stride, const float* z, int cout, int64_t P, const float* alpha, float calpha, int act,
-                         uint64_t lkey, uint32_t thresh, float keep, int dropout, float* dz, float* at) {
+                         uint64_t lkey, uint64_t idx0, uint32_t thresh, float keep, int dropout, float* dz, float* at) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= P * cout) return;
     const int64_t p = e / cout;
     const int co = (int)(e - p * cout);
     float g = dh[p * dh_stride + co];
-    if (dropout) g = dropout_keep(lkey, (uint64_t)e, thresh) ? g / keep : 0.0f;
+    if (dropout) g = dropout_keep(lkey, idx0 + (uint64_t)e, thresh) ? g / keep : 0.0f;
     const float zz = z[e];
     dz[e] = g * tact_grad(zz, alpha ? alpha[co] : calpha, act);
     if (at) at[e] = g * (zz < 0.0f ? zz : 0.0f);
@@ -344,10 +345,8 @@ __global__ __launch_bounds__(256) void tstats(const double* loss_part, int loss_
 }
 
 // one optimizer step over the flat buffers (TF's ApplyAdam / ApplyGradientDescent / ApplyMomentum), g scaled by the clip factor
-__global__ void topt(int kind, float* w, const float* g, float* m, float* v, int64_t count, const float* clip, const float* pw,
-                     float lr, float b1, float b2, float eps, float mu) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
+__device__ inline void opt_update(int kind, float* w, const float* g, float* m, float* v, int64_t e, const float* clip, const float* pw,
+                                  float lr, float b1, float b2, float eps, float mu) {
     const float gg = g[e] * clip[0];
     if (kind == DCSCN_OPTIMIZER_ADAM) {
         const float lr_t = lr * sqrtf(1.0f - pw[1]) / (1.0f - pw[0]);
@@ -363,8 +362,104 @@ __global__ void topt(int kind, float* w, const float* g, float* m, float* v, int
         w[e] = w[e] - lr * gg;
     }
 }
+__global__ void topt(int kind, float* w, const float* g, float* m, float* v, int64_t count, const float* clip, const float* pw,
+                     float lr, float b1, float b2, float eps, float mu) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    opt_update(kind, w, g, m, v, e, clip, pw, lr, b1, b2, eps, mu);
+}
 __global__ void tpowers(float* pw, float b1, float b2) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { pw[0] = pw[0] * b1; pw[1] = pw[1] * b2; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// data-parallel step (dcscn_train_local_gradients_* / dcscn_train_apply_records): every rank writes a record
+//   [count gradient floats | zeros up to a multiple of 4 | 4 doubles: image_loss, mse, n_local, total loss]
+// and every rank reduces all of them in rank order, so the replicas never differ by a bit.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kRecordTrailer = 8;   // floats: 4 doubles
+__host__ __device__ inline int64_t record_pad(int64_t count) { return (count + 3) / 4 * 4; }
+
+// padding and trailer of a record behind the gradient copy; stats = tstats' four doubles of the local batch
+__global__ void trecord_tail(float* rec, int64_t count, const double* stats, double n_local) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t pad = record_pad(count);
+    for (int64_t e = count; e < pad; ++e) rec[e] = 0.0f;
+    double* tr = reinterpret_cast<double*>(rec + pad);
+    tr[0] = stats[0]; tr[1] = stats[1]; tr[2] = n_local; tr[3] = stats[3];
+}
+
+// w[r] = n_r / sum n_r (double, summed in rank order); ok[0] = every n_r is > 0 and the sum is finite (else every weight is 0)
+__global__ void trank_weights(const float* records, int world, int64_t rf, int64_t pad, double* w, int* ok) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double sum = 0.0;
+    bool good = true;
+    for (int r = 0; r < world; ++r) {
+        const double n = reinterpret_cast<const double*>(records + (size_t)r * rf + pad)[2];
+        good = good && n > 0.0;              // (false for a NaN too)
+        sum += n;
+    }
+    good = good && sum <= 1.7976931348623157e308;
+    for (int r = 0; r < world; ++r) w[r] = good ? reinterpret_cast<const double*>(records + (size_t)r * rf + pad)[2] / sum : 0.0;
+    ok[0] = good ? 1 : 0;
+}
+
+// g[e] = (float) sum_{r = 0 .. world-1, in that order} w[r] * (double) records[r][e]; one thread per 4 floats, 16-byte loads over the
+// padded records and 16-byte stores (the ragged last quad of g is stored by element: g holds `count` floats, not the padding)
+__global__ __launch_bounds__(256) void treduce_ranks(const float* records, int world, int64_t rf, int64_t count, const double* w, float* g) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = q * 4;
+    if (e >= count) return;
+    tf32x4 v = *reinterpret_cast<const tf32x4*>(records + e);
+    double wr = w[0];
+    double a0 = wr * (double)v[0], a1 = wr * (double)v[1], a2 = wr * (double)v[2], a3 = wr * (double)v[3];
+    for (int r = 1; r < world; ++r) {
+        v = *reinterpret_cast<const tf32x4*>(records + (size_t)r * rf + e);
+        wr = w[r];
+        a0 += wr * (double)v[0]; a1 += wr * (double)v[1]; a2 += wr * (double)v[2]; a3 += wr * (double)v[3];
+    }
+    const tf32x4 out = {(float)a0, (float)a1, (float)a2, (float)a3};
+    if (e + 4 <= count) *reinterpret_cast<tf32x4*>(g + e) = out;
+    else
+        for (int i = 0; e + i < count; ++i) g[e + i] = out[i];
+}
+
+// tstats of the reduced step: stats[0] image_loss, [1] mse, [3] total loss = the weighted sums, in rank order, of the trailers;
+// [2] = the norm of the reduced gradient from tsumsq's partials, summed as tstats sums them; clip[0] by tstats' formula
+__global__ __launch_bounds__(256) void tstats_ranks(const float* records, int world, int64_t rf, int64_t pad, const double* w, const double* g2_part,
+                                                    int g2_blocks, double clip_norm, double* stats, float* clip) {
+    __shared__ double r[256];
+    const int t = threadIdx.x;
+    double g2 = 0.0;
+    for (int b = t; b < g2_blocks; b += 256) g2 += g2_part[b];
+    r[t] = g2;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) r[t] += r[t + o];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double* tr = reinterpret_cast<const double*>(records + pad);
+    double image = w[0] * tr[0], mse = w[0] * tr[1], total = w[0] * tr[3];
+    for (int k = 1; k < world; ++k) {
+        tr = reinterpret_cast<const double*>(records + (size_t)k * rf + pad);
+        image += w[k] * tr[0]; mse += w[k] * tr[1]; total += w[k] * tr[3];
+    }
+    const float norm = (float)sqrt(r[0]);
+    stats[0] = image; stats[1] = mse; stats[2] = norm; stats[3] = total;
+    const float c = (float)clip_norm;
+    clip[0] = clip_norm > 0.0 ? c / fmaxf(norm, c) : 1.0f;
+}
+
+// topt / tpowers behind a reduction: nothing moves when the records' patch counts did not form a batch (ok[0] = 0)
+__global__ void topt_ranks(const int* ok, int kind, float* w, const float* g, float* m, float* v, int64_t count, const float* clip, const float* pw,
+                           float lr, float b1, float b2, float eps, float mu) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count || !ok[0]) return;
+    opt_update(kind, w, g, m, v, e, clip, pw, lr, b1, b2, eps, mu);
+}
+__global__ void tpowers_ranks(const int* ok, float* pw, float b1, float b2) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && ok[0]) { pw[0] = pw[0] * b1; pw[1] = pw[1] * b2; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -407,6 +502,9 @@ struct TrainState {
     int w2_blocks = 0;
     std::vector<double> stats_host;
     bool stepped = false;          // a step has changed the variables since the inference plan was last packed
+    // dcscn_train_apply_records: [kNormBlocks] norm partials | 4 stats | clip (float) | ok (int) | [world] rank weights, as doubles
+    double* d_red = nullptr; size_t red_cap = 0;
+    hipEvent_t join_ev = nullptr;  // join_stream's event, made on first use
 };
 
 static int grid1(int64_t n) { return (int)((n + 255) / 256); }
@@ -566,7 +664,8 @@ static int launch_conv(dcscn_ctx* h, hipStream_t st, const float* in, int in_str
 }
 
 // forward + backward of one step (gradients into d_g, stats into d_stats); no host synchronisation
-static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const float* x2, const float* yt, uint64_t key, hipStream_t st) {
+static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const float* x2, const float* yt, uint64_t key, hipStream_t st,
+                         int64_t first_index = 0) {
     const dcscn_train_config& tc = t->tc;
     const int n = t->n, H = t->H, W = t->W;
     const int64_t P = (int64_t)n * H * W;
@@ -598,7 +697,8 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         if (L.dropout) {
             const TBuf& ob = t->bufs[L.out_buf];
             KTRY(h, hipLaunchKernelGGL(tact_fwd, dim3(grid1(px * L.cout)), dim3(256), 0, st, L.z, L.cout, px, L.a_t >= 0 ? t->d_w + t->off[L.a_t] : nullptr,
-                                       L.calpha, L.act, ob.h + L.out_off, ob.stride, dropout_layer_key(key, L.index), thresh, keep, drop ? 1 : 0));
+                                       L.calpha, L.act, ob.h + L.out_off, ob.stride, dropout_layer_key(key, L.index), (uint64_t)first_index * (uint64_t)(px / n * L.cout),
+                                       thresh, keep, drop ? 1 : 0));
         } else if (L.ps > 0) {
             const TBuf& ob = t->bufs[L.out_buf];
             const int C = L.cout / (L.ps * L.ps);
@@ -621,7 +721,8 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         if (L.dropout) {
             const TBuf& ob = t->bufs[L.out_buf];
             KTRY(h, hipLaunchKernelGGL(tact_bwd, dim3(grid1(px * L.cout)), dim3(256), 0, st, (const float*)(ob.g + L.out_off), ob.stride, (const float*)L.z, L.cout, px,
-                                       prelu ? t->d_w + t->off[L.a_t] : nullptr, L.calpha, L.act, dropout_layer_key(key, L.index), thresh, keep, drop ? 1 : 0,
+                                       prelu ? t->d_w + t->off[L.a_t] : nullptr, L.calpha, L.act, dropout_layer_key(key, L.index),
+                                       (uint64_t)first_index * (uint64_t)(px / n * L.cout), thresh, keep, drop ? 1 : 0,
                                        t->dz, prelu ? t->at : nullptr));
         } else if (L.ps > 0) {
             const TBuf& ob = t->bufs[L.out_buf];
@@ -717,11 +818,37 @@ static int host_step(dcscn_ctx* h, const float* x, const float* x2, const float*
     return read_stats(h, t, stats, st);
 }
 
+// later host-buffer steps, forwards and tensor reads run on the handle's stream: order it behind the caller's
+static int join_stream(dcscn_ctx* h, hipStream_t st) {
+    if (st == h->stream) return DCSCN_OK;
+    TrainState* t = h->train;
+    if (!t->join_ev) HIP_TRY(h, hipEventCreateWithFlags(&t->join_ev, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(t->join_ev, st));
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, t->join_ev, 0));
+    return DCSCN_OK;
+}
+
+static int check_record(dcscn_ctx* h, const void* rec, int64_t first_index, const char* what) {
+    if (!rec) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: null record buffer", what);
+    if ((uintptr_t)rec % 16 != 0) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: the record buffer is not 16-byte aligned", what);
+    if (first_index < 0) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: first_index %lld < 0", what, (long long)first_index);
+    return DCSCN_OK;
+}
+
+// the gradient of the batch just run (d_g) and its stats as a record at `rec`, on `st`
+static int write_record(dcscn_ctx* h, TrainState* t, int n, float* rec, hipStream_t st) {
+    HIP_TRY(h, hipMemcpyAsync(rec, t->d_g, (size_t)t->count * 4, hipMemcpyDeviceToDevice, st));
+    KTRY(h, hipLaunchKernelGGL(trecord_tail, dim3(1), dim3(1), 0, st, rec, t->count, (const double*)t->d_stats, (double)n));
+    return join_stream(h, st);
+}
+
 void train_free(dcscn_ctx* h) {
     TrainState* t = h->train;
     if (!t) return;
     for (float* p : {t->d_w, t->d_g, t->d_m, t->d_v, t->d_wd, t->d_pw})
         if (p) (void)hipFree(p);
+    if (t->d_red) (void)hipFree(t->d_red);
+    if (t->join_ev) (void)hipEventDestroy(t->join_ev);
     if (t->arena) (void)hipFree(t->arena);
     delete t;
     h->train = nullptr;
@@ -821,14 +948,7 @@ int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, con
     if ((rc = run_gradients(h, t, x, x2, y_true, dropout_key, st))) return rc;
     if ((rc = apply_update(h, t, lr, st))) return rc;
     if ((rc = read_stats(h, t, stats, st))) return rc;
-    if (st != h->stream) {   // later host-buffer steps and forwards run on the handle's stream
-        hipEvent_t ev;
-        HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIP_TRY(h, hipEventRecord(ev, st));
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, ev, 0));
-        HIP_TRY(h, hipEventDestroy(ev));
-    }
-    return DCSCN_OK;
+    return join_stream(h, st);
 }
 
 int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr, uint64_t dropout_key,
@@ -844,6 +964,81 @@ int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, 
     if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st))) return rc;
     if ((rc = apply_update(h, t, lr, st))) return rc;
     return read_stats(h, t, stats, st);
+}
+
+int64_t dcscn_train_record_floats(dcscn_handle h) {
+    if (!h) return 0;
+    int64_t count = 0;
+    for (const TensorSpec& ts : h->tensors) count += (int64_t)ts.data.size();
+    return record_pad(count) + kRecordTrailer;
+}
+
+int dcscn_train_local_gradients_device(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width,
+                                       uint64_t dropout_key, int64_t first_index, float* record_out, void* stream) {
+    int rc = check_step(h, x, x2, y_true, n, height, width);
+    if (rc) return rc;
+    if ((rc = check_record(h, record_out, first_index, "dcscn_train_local_gradients_device"))) return rc;
+    TrainState* t = h->train;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = carve(h, t, n, height, width))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = run_gradients(h, t, x, x2, y_true, dropout_key, st, first_index))) return rc;
+    return write_record(h, t, n, record_out, st);
+}
+
+int dcscn_train_local_gradients_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, uint64_t dropout_key,
+                                        int64_t first_index, float* record_out, void* stream) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    if ((rc = check_record(h, record_out, first_index, "dcscn_train_local_gradients_patches"))) return rc;
+    TrainState* t = h->train;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = carve(h, t, n, lr_size, lr_size))) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;   // train_data.hip
+    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st, first_index))) return rc;
+    return write_record(h, t, n, record_out, st);
+}
+
+int dcscn_train_apply_records(dcscn_handle h, const float* records, int world, double lr, double* stats, void* stream) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_train_apply_records before dcscn_finalize");
+    if (!h->train) return fail(h, DCSCN_ERR_STATE, "dcscn_train_apply_records before dcscn_train_begin");
+    if (world < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_apply_records: world %d < 1", world);
+    int rc = check_record(h, records, 0, "dcscn_train_apply_records");
+    if (rc) return rc;
+    TrainState* t = h->train;
+    const dcscn_train_config& tc = t->tc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((rc = grow(h, &t->d_red, &t->red_cap, (size_t)kNormBlocks + 8 + (size_t)world, st))) return rc;
+    double *g2p = t->d_red, *d_stats = g2p + kNormBlocks, *w = d_stats + 8;
+    float* clip = reinterpret_cast<float*>(d_stats + 4);
+    int* ok = reinterpret_cast<int*>(d_stats + 5);
+    const int64_t pad = record_pad(t->count), rf = pad + kRecordTrailer;
+    KTRY(h, hipLaunchKernelGGL(trank_weights, dim3(1), dim3(1), 0, st, records, world, rf, pad, w, ok));
+    KTRY(h, hipLaunchKernelGGL(treduce_ranks, dim3(grid1(pad / 4)), dim3(256), 0, st, records, world, rf, t->count, (const double*)w, t->d_g));
+    const int64_t gchunk = (t->count + kNormBlocks - 1) / kNormBlocks;
+    KTRY(h, hipLaunchKernelGGL(tsumsq, dim3(kNormBlocks), dim3(256), 0, st, (const float*)t->d_g, t->count, gchunk, g2p));
+    KTRY(h, hipLaunchKernelGGL(tstats_ranks, dim3(1), dim3(256), 0, st, records, world, rf, pad, (const double*)w, (const double*)g2p, kNormBlocks,
+                               tc.clipping_norm, d_stats, clip));
+    KTRY(h, hipLaunchKernelGGL(topt_ranks, dim3(grid1(t->count)), dim3(256), 0, st, (const int*)ok, tc.optimizer, t->d_w, (const float*)t->d_g, t->d_m,
+                               t->d_v, t->count, (const float*)clip, (const float*)t->d_pw, (float)lr, (float)tc.beta1, (float)tc.beta2,
+                               (float)tc.epsilon, (float)tc.momentum));
+    if (tc.optimizer == DCSCN_OPTIMIZER_ADAM)
+        KTRY(h, hipLaunchKernelGGL(tpowers_ranks, dim3(1), dim3(1), 0, st, (const int*)ok, t->d_pw, (float)tc.beta1, (float)tc.beta2));
+    t->stepped = true;
+    if ((rc = join_stream(h, st))) return rc;
+    if (!stats) return DCSCN_OK;
+    double host[6];
+    HIP_TRY(h, hipMemcpyAsync(host, d_stats, sizeof host, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    int good;
+    memcpy(&good, &host[5], sizeof good);
+    if (!good) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_apply_records: a patch count of the %d records is not > 0, or their sum is not finite; nothing was updated", world);
+    std::copy(host, host + 4, stats);
+    return DCSCN_OK;
 }
 
 // "<var>", "<var>/grad", "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power"

@@ -31,6 +31,8 @@ EXPORTED_SYMBOLS = (
     "dcscn_train_begin", "dcscn_train_step", "dcscn_train_step_device", "dcscn_train_gradients", "dcscn_get_tensor",
     "dcscn_set_train_tensor", "dcscn_train_add_image", "dcscn_train_build_batch", "dcscn_train_step_patches",
     "dcscn_psnr_ssim", "dcscn_evaluate_rgb_metrics",
+    "dcscn_train_record_floats", "dcscn_train_local_gradients_device", "dcscn_train_local_gradients_patches",
+    "dcscn_train_apply_records",
 )
 
 # dcscn_optimizer; the names of helper/args.py --optimizer
@@ -198,6 +200,11 @@ def load_library():
     lib.dcscn_train_add_image.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_int32)]
     lib.dcscn_train_build_batch.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, fp, fp, fp]
     lib.dcscn_train_step_patches.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_double, c.c_uint64, dp]
+    lib.dcscn_train_record_floats.argtypes = [vp]
+    lib.dcscn_train_record_floats.restype = c.c_int64
+    lib.dcscn_train_local_gradients_device.argtypes = [vp, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_uint64, c.c_int64, vp, vp]
+    lib.dcscn_train_local_gradients_patches.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_uint64, c.c_int64, vp, vp]
+    lib.dcscn_train_apply_records.argtypes = [vp, vp, c.c_int, c.c_double, dp, vp]
     if lib.dcscn_abi_version() != ABI_VERSION:
         raise EngineError(5, "ABI mismatch: library %d, binding %d" % (lib.dcscn_abi_version(), ABI_VERSION))
     _lib = lib
@@ -548,6 +555,33 @@ class Engine:
         self._check(self._lib.dcscn_train_step_patches(self._h, ptr, len(p), int(lr_size), float(max_value), float(lr),
                                                        int(dropout_key) & (2 ** 64 - 1), stats))
         return tuple(stats)
+
+    # ---- data-parallel training ("Data-parallel training" in include/dcscn.h): records in device memory, pointers as ints ----
+    def train_record_floats(self):
+        """Length in float32 values of a gradient record of this graph."""
+        return int(self._lib.dcscn_train_record_floats(self._h))
+
+    def train_local_gradients_device(self, x_ptr, x2_ptr, y_ptr, n, h, w, record_ptr, dropout_key=0, first_index=0, stream=None):
+        """Gradient of the shard [n, h, w] (device pointers) whose first patch is patch ``first_index`` of the global batch, written
+        as a record to ``record_ptr``; no update, no synchronisation.  ``stream``: a hipStream_t as an int, None / 0 = the handle's own."""
+        self._check(self._lib.dcscn_train_local_gradients_device(
+            self._h, ctypes.c_void_p(x_ptr), ctypes.c_void_p(x2_ptr), ctypes.c_void_p(y_ptr), int(n), int(h), int(w),
+            int(dropout_key) & (2 ** 64 - 1), int(first_index), ctypes.c_void_p(record_ptr), ctypes.c_void_p(stream) if stream else None))
+
+    def train_local_gradients_patches(self, patches, lr_size, record_ptr, max_value=255.0, dropout_key=0, first_index=0, stream=None):
+        """train_local_gradients_device on the shard train_build_batch would build from ``patches``, built on the device."""
+        p, ptr = self._patches(patches)
+        self._check(self._lib.dcscn_train_local_gradients_patches(
+            self._h, ptr, len(p), int(lr_size), float(max_value), int(dropout_key) & (2 ** 64 - 1), int(first_index),
+            ctypes.c_void_p(record_ptr), ctypes.c_void_p(stream) if stream else None))
+
+    def train_apply_records(self, records_ptr, world, lr, stream=None, want_stats=True):
+        """Reduce the ``world`` records at ``records_ptr`` ([world, train_record_floats()] float32 on the device) in rank order and
+        take the optimizer step; with want_stats the call synchronises and returns the global batch's stats of train_step."""
+        stats = (ctypes.c_double * 4)() if want_stats else None
+        self._check(self._lib.dcscn_train_apply_records(self._h, ctypes.c_void_p(records_ptr), int(world), float(lr), stats,
+                                                        ctypes.c_void_p(stream) if stream else None))
+        return tuple(stats) if want_stats else None
 
     def _numel(self, name):
         base = name

@@ -28,8 +28,7 @@ class LoadError(Exception):
 # ---- filesystem ---------------------------------------------------------------------------------
 
 def make_dir(directory):
-    if not os.path.exists(directory):
-        os.makedirs(directory)
+    os.makedirs(directory, exist_ok=True)       # (several ranks of one launch create the same directory at once)
 
 
 def get_files_in_directory(path):

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import ckpt, engine, frozen, imaging as util
+from . import ckpt, engine, frozen, imaging as util, shard
 
 BICUBIC_METHOD_STRING = "bicubic"
 
@@ -128,6 +128,11 @@ class SuperResolution:
         self._device_images = {}            # filename -> image id of the images uploaded to _train_engine
         self._patches = None                # the batch build_input_batch drew, for the next train_batch
         self._pending_slots = None          # optimizer slots of a checkpoint loaded before training began
+        # train.py under torch.distributed.run: a shard.Group whose ranks each train on their shard of every batch and apply the
+        # same rank-ordered reduction of all shards' gradients (include/dcscn.h "Data-parallel training"); None: one process
+        self.train_group = None
+        self._train_stream = None           # the torch stream the data-parallel step is ordered on
+        self._record = None                 # this rank's gradient record (a torch tensor on the device)
 
         self.name = self.get_model_name(model_name)
 
@@ -254,6 +259,8 @@ class SuperResolution:
                 tensors[name] = np.zeros(shape, np.float32)
             else:
                 tensors[name] = np.full(shape, 0.1, np.float32)
+        if self._data_parallel():
+            tensors = self.train_group.broadcast_object(tensors)      # every replica starts from rank 0's draw
         self._pending_init = tensors
         print("Model initialized.")
 
@@ -274,6 +281,8 @@ class SuperResolution:
         if self._train_flags is not None:
             # a training run: the variables and, when the checkpoint has them, the optimizer slots (tf.train.Saver restores both)
             tensors = ckpt.load_checkpoint(filename, include_optimizer_slots=True)
+            if self._data_parallel():
+                tensors = self.train_group.broadcast_object(tensors)  # rank 0's variables and slots, whatever the other ranks read
             slots = {k: v for k, v in tensors.items() if ckpt.is_optimizer_slot(k)}
             self.load_weights({k: v for k, v in tensors.items() if k not in slots})
             self._pending_slots = slots or None
@@ -367,11 +376,16 @@ class SuperResolution:
     def _training_active(self):
         return self._train_engine is not None and self._train_engine is self._engine
 
+    def _data_parallel(self):
+        return self.train_group is not None and self.train_group.world > 1
+
     def _ready_training(self):
         if self._train_flags is None:
             raise RuntimeError("train_batch() before build_optimizer()")
         eng = self._ready_engine()
         if self._train_engine is not eng:
+            if self._data_parallel():
+                self.step = self.train_group.broadcast_object(self.step)   # the dropout key counts steps: rank 0's, when resuming
             eng.train_begin(self._train_flags)
             self._train_engine = eng
             self._device_images = {}
@@ -412,6 +426,33 @@ class SuperResolution:
             raise NotImplementedError("training batches are built for channels = 1 (Y) only")
         self._patches = [self.train.next_patch() for _ in range(self.batch_num)]
 
+    def training_digest(self):
+        """sha256 over the variables, optimizer slots and beta powers of the running training, in name order: equal on two
+        replicas exactly when they hold the same bits."""
+        import hashlib
+        digest = hashlib.sha256()
+        for name, value in sorted(self._training_tensors().items()):
+            digest.update(name.encode())
+            digest.update(np.ascontiguousarray(value, dtype=np.float32).tobytes())
+        return digest.hexdigest()
+
+    def _train_shard_step(self, eng, descriptors, first_index):
+        """The data-parallel step: this rank's shard of the batch (its patches, the first of them patch ``first_index`` of the
+        batch) -> its record, all records gathered, the same rank-ordered reduction and update on every rank.  Returns the stats
+        of the whole batch."""
+        import torch
+        group = self.train_group
+        device = torch.device("cuda", eng.device)
+        if self._record is None or self._record.device != device:
+            self._train_stream = torch.cuda.Stream(device=device)
+            self._record = torch.empty(eng.train_record_floats(), dtype=torch.float32, device=device)
+        with torch.cuda.stream(self._train_stream):
+            stream = self._train_stream.cuda_stream
+            eng.train_local_gradients_patches(descriptors, self.train.batch_image_size, self._record.data_ptr(), max_value=self.max_value,
+                                              dropout_key=self.dropout_key(), first_index=first_index, stream=stream)
+            records = group.all_gather_records(self._record)
+            return eng.train_apply_records(records.data_ptr(), group.world, self.lr, stream=stream)
+
     def dropout_key(self):
         return (int(self.dropout_seed) << 32) + int(self.step)
 
@@ -420,18 +461,26 @@ class SuperResolution:
         eng = self._ready_training()
         if self._patches is not None:      # drawn by build_input_batch: built on the device from the uploaded images
             patches, self._patches = self._patches, None
+            begin, end = 0, len(patches)
+            if self._data_parallel():      # every rank drew the whole batch; it uploads and cuts only its own shard
+                begin, end = shard.train_shard(len(patches), self.train_group.rank, self.train_group.world)
             descriptors = []
-            for filename, top, left, fliplr in patches:
+            for filename, top, left, fliplr in patches[begin:end]:
                 image_id = self._device_images.get(filename)
                 if image_id is None:
                     image_id = self._device_images[filename] = eng.train_add_image(self.train.image(filename))
                 descriptors.append((image_id, top, left, fliplr))
-            image_loss, mse, _, _ = eng.train_step_patches(descriptors, self.train.batch_image_size, self.lr, max_value=self.max_value,
-                                                           dropout_key=self.dropout_key())
+            if self._data_parallel():
+                image_loss, mse, _, _ = self._train_shard_step(eng, descriptors, begin)
+            else:
+                image_loss, mse, _, _ = eng.train_step_patches(descriptors, self.train.batch_image_size, self.lr, max_value=self.max_value,
+                                                               dropout_key=self.dropout_key())
         else:                              # arrays assigned to batch_input, batch_input_bicubic, batch_true
             x = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input])
             x2 = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_input_bicubic])
             y = np.stack([np.asarray(a, np.float32).reshape(a.shape[0], a.shape[1], 1) for a in self.batch_true])
+            if self._data_parallel():
+                raise NotImplementedError("data-parallel training takes the batches build_input_batch draws, not assigned arrays")
             image_loss, mse, _, _ = eng.train_step(x, x2, y, self.lr, dropout_key=self.dropout_key())
         self.training_loss_sum += image_loss
         self.training_psnr_sum += 0 if mse == 0 else 20 * math.log(self.max_value / math.sqrt(mse), 10)

@@ -4,6 +4,10 @@ The DCSCN forward pass has no cross-image coupling, so multi-GPU is an embarrass
 partition: rank r of W takes a contiguous shard, weights are replicated (a few MB), and nothing is
 exchanged on the data path.  ``torch.distributed`` (RCCL on GPUs, gloo on CPU) is used only to
 gather small per-item results (PSNR values, timings) on rank 0.
+
+Data-parallel training (train.py) shards every batch the same way: rank r computes the gradient of its
+contiguous shard into a record (include/dcscn.h, "Data-parallel training"), ``Group.all_gather_records``
+exchanges the records, and every rank reduces all of them in rank order on its own device.
 """
 
 import os
@@ -39,6 +43,35 @@ def split_ensemble(n_items, world, self_ensemble):
     return world > 1 and self_ensemble > 1 and n_items < 2 * world
 
 
+RECORD_TRAILER_FLOATS = 8          # 4 doubles: image_loss, mse, n_local, total loss
+
+
+def record_floats(n_values):
+    """Length of a gradient record of a graph with ``n_values`` variable elements: the gradient padded to a 16-byte
+    boundary, then the trailer (what dcscn_train_record_floats returns)."""
+    if n_values < 0:
+        raise ValueError("bad element count %d" % n_values)
+    return (n_values + 3) // 4 * 4 + RECORD_TRAILER_FLOATS
+
+
+def train_shard(batch_num, rank, world):
+    """[begin, end) of the patches of a ``batch_num`` batch that ``rank`` trains on; ``begin`` is the shard's first_index."""
+    refusal = train_batch_refusal(batch_num, world)
+    if refusal:
+        raise ValueError(refusal)
+    return shard_bounds(batch_num, rank, world)
+
+
+def train_batch_refusal(batch_num, world):
+    """None when every one of ``world`` ranks gets at least one patch of a ``batch_num`` batch, else the message train.py prints."""
+    if world < 1:
+        return "bad world size %d" % world
+    if batch_num < world:
+        return ("Error. --batch_num=%d is smaller than the %d ranks of this launch: every rank needs at least one patch per step; "
+                "raise --batch_num or launch fewer ranks." % (batch_num, world))
+    return None
+
+
 class Group:
     """The process group of this launch (a single process when not launched by torch.distributed.run)."""
 
@@ -69,6 +102,30 @@ class Group:
     def barrier(self):
         if self.world > 1:
             self._dist.barrier()
+
+    def broadcast_object(self, obj, src=0):
+        """``obj`` of rank ``src`` on every rank."""
+        if self.world == 1:
+            return obj
+        box = [obj if self.rank == src else None]
+        self._dist.broadcast_object_list(box, src=src)
+        return box[0]
+
+    def all_gather_records(self, record):
+        """Every rank's gradient record (a flat float32 torch tensor, the same length on every rank) as one
+        [world, length] tensor in rank order, on ``record``'s device and ordered on the current stream.  RCCL gathers
+        device tensors in place; the gloo group of the shared-device test rig goes through host tensors and back."""
+        import torch
+        if self.world == 1:
+            return record.reshape(1, -1)
+        if self._dist.get_backend() == "nccl":
+            out = torch.empty((self.world, record.numel()), dtype=record.dtype, device=record.device)
+            self._dist.all_gather_into_tensor(out, record)
+            return out
+        host = record.cpu()                                   # (on the current stream: behind the kernels that wrote the record)
+        parts = [torch.empty_like(host) for _ in range(self.world)]
+        self._dist.all_gather(parts, host)
+        return torch.stack(parts).to(record.device)
 
     def ensemble_mean(self, image, bicubic, n, forward_one, flip):
         """Distributed self-ensemble of ONE image (DCSCN.py:559-573): transform t runs on rank t % world, the float32 results

@@ -339,7 +339,8 @@ int64_t dcscn_workspace_bytes(dcscn_handle h);
 int dcscn_num_presplit_tensors(dcscn_handle h);
 
 /* ---------------------------------------------------------------------------------------------------------------------
- * Training (DCSCN.py:334-425, 727-769): single device, f32, non-separable pixel-shuffler nets only.
+ * Training (DCSCN.py:334-425, 727-769): f32, non-separable pixel-shuffler nets only; one device per handle, several handles
+ * (one per rank) train data-parallel through the record calls below.
  *
  * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no split16, no Winograd), with
  * dropout after the activator of every conv that has one (CNN1..L, A1, B1, B2, C, the non-final R-CNN layers; not the Up-PS
@@ -363,6 +364,9 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  * Reference values: splitmix64(0) = 0xE220A8397B1DCDAF; for dropout_key = 1, layer = 0: layer_key = 0xBEEB8DA1658EEC67 and
  * splitmix64(layer_key ^ 0) >> 40 = 0x778B1A, splitmix64(layer_key ^ 1) >> 40 = 0x3ED40B.
  * keep_prob = 1 turns dropout off.
+ * A shard of a data-parallel step (dcscn_train_local_gradients_*, first_index = the index of the shard's first patch within the
+ * global batch) counts n from first_index: idx = first_index * H * W * C + the shard-local idx above, H, W at the layer's
+ * resolution.  The masks of a sharded batch are therefore the masks of the whole batch; first_index = 0 is the rule above.
  *
  * Variables, their gradients and the slots live on the device in flat f32 buffers, checkpoint (HWIO) layout.  Tensor names
  * (TF's, so checkpoints interoperate): "<var>", "<var>/grad" (gradient of the total loss BEFORE clipping, of the last step
@@ -430,6 +434,33 @@ int dcscn_train_build_batch(dcscn_handle h, const dcscn_patch* patches, int n, i
  * crosses PCIe.  Synchronises only when stats != NULL (the 4 doubles of dcscn_train_step). */
 int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr,
                              uint64_t dropout_key, double* stats);
+/* Data-parallel training: every rank holds a full replica (variables, slots, beta powers) on its own handle.  Per step each
+ * rank computes the gradient of its shard of the global batch into a RECORD, the ranks exchange the records (any all-gather:
+ * the library does not communicate), and every rank reduces all records in rank order and applies the same update -- the
+ * replicas stay bit-identical without ever exchanging weights, and two runs give the same bits.
+ * A record is dcscn_train_record_floats(h) float32 values in device memory, 16-byte aligned:
+ *   [0, count)            the flat gradient of the shard's loss (local mean image loss + the l2 term, what dcscn_train_gradients
+ *                         computes), variables in dcscn_tensor_info order, each in checkpoint layout
+ *   [count, pad)          zeros, pad = count rounded up to a multiple of 4
+ *   [pad, pad + 8)        4 doubles, bit for bit: image_loss, mse, n_local (the shard's patch count), total loss
+ * dcscn_train_apply_records takes `world` records laid out [world][record_floats] and computes, on the device, with no atomics:
+ *   w_r = n_r / sum n_r (double);  g[e] = (float) sum over r = 0 .. world-1, in that order, of w_r * (double) g_r[e]
+ * (uneven shards give the exact mean over the global batch; the l2 term every rank added comes out once), the global norm of g
+ * in the order dcscn_train_step sums it, the stats as the same weighted sums of the trailers (stats[2] = the norm of g), the
+ * clip factor, and then the update rule above.  With world = 1 and first_index = 0 the two calls give dcscn_train_step's bits.
+ * Both kinds of call enqueue on `stream` (NULL = the handle's) and do not synchronise, except apply_records with stats != NULL.
+ * "<var>/grad" reads the shard's gradient after a local_gradients call and the reduced one after apply_records.
+ * Refused: before dcscn_train_begin DCSCN_ERR_STATE; world < 1, first_index < 0, null or misaligned pointers, n < 1
+ * DCSCN_ERR_INVALID_ARG.  Records of which one n_local is not > 0, or whose n_local sum to a non-finite value (so also a sum of
+ * zero), leave variables, slots and powers untouched; the call reports that as DCSCN_ERR_INVALID_ARG when stats != NULL (without
+ * stats it does not read the device back).  "<var>/grad" reads zeros after such a call, not the last local gradient. */
+int64_t dcscn_train_record_floats(dcscn_handle h);
+int dcscn_train_local_gradients_device(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width,
+                                       uint64_t dropout_key, int64_t first_index, float* record_out, void* stream);
+/* The same with the shard built on the device from dcscn_patch descriptors, as dcscn_train_step_patches builds its batch. */
+int dcscn_train_local_gradients_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value,
+                                        uint64_t dropout_key, int64_t first_index, float* record_out, void* stream);
+int dcscn_train_apply_records(dcscn_handle h, const float* records, int world, double lr, double* stats, void* stream);
 /* Read a variable (any time after its dcscn_set_tensor; the trained value while training), a gradient or a slot: `count`
  * must equal its number of values. */
 int dcscn_get_tensor(dcscn_handle h, const char* name, float* out, int64_t count);
