@@ -144,3 +144,103 @@ def test_bad_patches_and_calls_before_train_begin_are_refused(oracle):
         x, x2, y = eng.train_build_batch([ok], 8)                      # the handle still works
         assert x.shape == (1, 8, 8, 1) and x2.shape == y.shape == (1, 16, 16, 1) and np.all(y == 16.0)      # Y of black
         assert len(eng.train_step_patches([ok, ok], 8, 1e-3)) == 4
+
+
+# ---------------------------------------------------------------------------------------------
+# batches of more than 32 patches: batch_gather and batch_finish are launched once per 32 patches (kChunk of csrc/train_data.hip),
+# their outputs offset by whole chunks, and the slot numbers of the grey and of the RGB patches run on across the launches
+# ---------------------------------------------------------------------------------------------
+CHUNK = 32
+
+
+def _kinds(d, patches):
+    """Channels of every patch's image: 1 = grey (uint8 planes on the device), 3 = RGB (float planes)."""
+    return [d.image(p[0]).shape[2] for p in patches]
+
+
+def _seed_where(data_dir, scale, size, count, accept):
+    """The first draw seed whose ``count`` patches' kinds satisfy ``accept`` (the order of the files of a directory, and with it
+    what a seed draws, is the file system's: the seed is searched, on the CPU, and the property asserted)."""
+    d = _dataset(data_dir, scale, size)
+    for seed in range(1, 200):
+        random.seed(seed)
+        d.init_batch_index()
+        if accept(_kinds(d, [d.next_patch() for _ in range(count)])):
+            return seed
+    raise AssertionError("no seed below 200 draws the batch this test needs")
+
+
+def _both_sides(kinds):
+    """Grey and RGB patches below index 32 and at or above it."""
+    return set(kinds[:CHUNK]) == {1, 3} and set(kinds[CHUNK:]) == {1, 3}
+
+
+def _assert_crosses(kinds, count, last=None):
+    assert len(kinds) == count > CHUNK
+    assert set(kinds[:CHUNK]) == {1, 3}, kinds
+    if last is None:
+        assert set(kinds[CHUNK:]) == {1, 3}, kinds
+    else:
+        assert kinds[CHUNK:] == [last], kinds                # 33 patches: the one patch of the second launch, of the kind asked for
+    for kind in set(kinds[CHUNK:]):
+        # a patch of the second launch takes a slot behind the patches of its kind in the first: the carry-over of the slot numbers
+        assert kinds[:CHUNK].count(kind) >= 1, (kind, kinds)
+
+
+def _crossing_cases(data_dir, scale, size):
+    """(count, seed, kind of patch 32 or None): 64 and 65 patches with both kinds on both sides of index 32, and 33 patches twice,
+    patch 32 once grey and once RGB (one draw of 33 has a single patch at or above 32, so two draws cover both kinds there)."""
+    cases = [(count, _seed_where(data_dir, scale, size, count, _both_sides), None) for count in (64, 65)]
+    for last in (1, 3):
+        cases.append((33, _seed_where(data_dir, scale, size, 33, lambda k: set(k[:CHUNK]) == {1, 3} and k[CHUNK] == last), last))
+    return cases
+
+
+def _check_crossing(oracle, data_dir, scale, size, cases):
+    with _engine(oracle, scale) as eng:
+        for i, (count, seed, last) in enumerate(cases):
+            max_value = (255.0, 1.0)[i % 2]
+            d, patches, want = _draw(data_dir, scale, size, count, seed=seed, max_value=max_value)
+            kinds = _kinds(d, patches)
+            _assert_crosses(kinds, count, last)
+            print("%d patches at scale %d size %d, seed %d, max_value %g: %d grey and %d RGB below index 32, %d and %d from it on"
+                  % (count, scale, size, seed, max_value, kinds[:CHUNK].count(1), kinds[:CHUNK].count(3), kinds[CHUNK:].count(1),
+                     kinds[CHUNK:].count(3)))
+            _check_batch(eng, d, patches, size, max_value, want)
+
+
+@pytest.mark.parametrize("scale,size", [(2, 7), (4, 3)])
+def test_synthetic_batches_across_the_32_patch_launch_equal_the_host_loader(oracle, tmp_path, scale, size):
+    data_dir = _synthetic_dir(tmp_path, scale * size)
+    _check_crossing(oracle, data_dir, scale, size, _crossing_cases(data_dir, scale, size))
+
+
+def test_set14_batch_across_the_32_patch_launch_equals_the_host_loader(oracle):
+    scale, size = 2, 16
+    _check_crossing(oracle, SET14, scale, size, [(65, _seed_where(SET14, scale, size, 65, _both_sides), None)])
+
+
+def test_step_on_33_patches_equals_the_step_on_the_loaders_arrays(oracle):
+    """train_step_patches on 33 patches (the 33rd a grey one, behind grey ones of the first launch) against train_step on what
+    load_batch_image cuts of the same patches: stats and state bit for bit, c-DCSCN x2, clipped adam with dropout."""
+    scale, size, count = 2, 8, 33
+    seed = _seed_where(SET14, scale, size, count, lambda k: set(k[:CHUNK]) == {1, 3} and k[CHUNK] == 1)
+    d, patches, want = _draw(SET14, scale, size, count, seed=seed, max_value=255.0)
+    _assert_crosses(_kinds(d, patches), count, 1)
+    cfg = oracle.make_config(**CONFIGS["L7_F32to8_x2"])
+    names = list(oracle.synthetic_weights(cfg, seed=0))
+    with _engine(oracle, scale) as dev, _engine(oracle, scale) as host:
+        ids = {}
+        for f, _, _, _ in patches:
+            if f not in ids:
+                ids[f] = dev.train_add_image(d.image(f))
+        for step in range(2):
+            got = dev.train_step_patches([(ids[f], t, l, fl) for f, t, l, fl in patches], size, 1e-3, dropout_key=77 + step)
+            ref = host.train_step(*want, 1e-3, dropout_key=77 + step)
+            print("step %d: stats %r" % (step, got))
+            assert np.array_equal(np.array(got).view(np.uint64), np.array(ref).view(np.uint64)), (got, ref)
+            for k in names:
+                for s in ("", "/Adam", "/Adam_1", "/grad"):
+                    assert np.array_equal(dev.get_tensor(k + s).view(np.uint32), host.get_tensor(k + s).view(np.uint32)), (step, k + s)
+            for s in ("beta1_power", "beta2_power"):
+                assert np.array_equal(dev.get_tensor(s).view(np.uint32), host.get_tensor(s).view(np.uint32)), (step, s)

@@ -286,6 +286,104 @@ def test_refusals():
         assert not np.array_equal(before["CNN1/conv_W"], eng.get_tensor("CNN1/conv_W"))
 
 
+# ---- G: the patch route (dcscn_train_local_gradients_patches), the one SuperResolution._train_shard_step takes -------------------
+
+LR_SIZE = 8
+
+
+@functools.lru_cache(maxsize=None)
+def _set14_draw(scale, count, max_value):
+    """(dataset, descriptors, the host loader's arrays) of `count` Set14 patches in which grey img_003 and RGB images both occur in
+    the first 5; the seed is searched on the CPU (what a seed draws depends on the directory's file order)."""
+    from test_train_batches_hip import SET14, _draw, _kinds, _seed_where
+    mixed = lambda kinds: set(kinds[:5]) == {1, 3}         # (Set14 has one grey image: at most one grey patch per 14 draws)
+    seed = _seed_where(SET14, scale, LR_SIZE, count, mixed)
+    d, patches, want = _draw(SET14, scale, LR_SIZE, count, seed=seed, max_value=max_value)
+    assert mixed(_kinds(d, patches))
+    return d, tuple(patches), tuple(want)
+
+
+def _descriptors(eng, d, patches, ids):
+    """Device descriptors of `patches`; `ids` = this engine's {filename: image id}, filled as images are first used."""
+    out = []
+    for f, top, left, flip in patches:
+        if f not in ids:
+            ids[f] = eng.train_add_image(d.image(f))
+        out.append((ids[f], top, left, flip))
+    return out
+
+
+class PatchRig(Rig):
+    """Rig whose ranks compute their records from patch descriptors, each rank uploading only the images of its own shard."""
+
+    def __init__(self, name, splits, **flags):
+        super().__init__(name, splits, **flags)
+        self.ids = [{} for _ in splits]
+
+    def local_patches(self, d, patches, key, max_value=255.0):
+        for r, eng in enumerate(self.engines):
+            b, e = int(self.bounds[r]), int(self.bounds[r + 1])
+            eng.train_local_gradients_patches(_descriptors(eng, d, patches[b:e], self.ids[r]), LR_SIZE, self.records[r].data_ptr(),
+                                              max_value=max_value, dropout_key=key, first_index=b, stream=self.stream.cuda_stream)
+
+
+@pytest.mark.parametrize("max_value", [255.0, 1.0])
+@pytest.mark.parametrize("name", [X2, X4])
+def test_patch_route_writes_the_record_of_the_array_route_bit_for_bit(name, max_value):
+    """For the shards 3+2 and 2+2+1 of one batch: the record from descriptors equals the record from the host loader's arrays of the
+    same shard with the same key and first_index, over the whole record -- gradient, padding, trailer.  Fails if first_index does
+    not reach the dropout hash on the patch route (keep 0.8), or if the shard's batch is not the loader's."""
+    cfg, _ = _net(name)
+    d, patches, want = _set14_draw(cfg["scale"], 5, max_value)
+    dev = _device(want)
+    for splits in ((3, 2), (2, 2, 1)):
+        with PatchRig(name, splits, dropout_rate=0.8) as by_patch, Rig(name, splits, dropout_rate=0.8) as by_array:
+            by_patch.local_patches(d, patches, KEY, max_value)
+            by_array.local(dev, KEY)
+            torch.cuda.synchronize()
+            a, b = by_patch.records.cpu().numpy(), by_array.records.cpu().numpy()
+        assert np.any(a[:, :1000]) and a.shape == b.shape == (len(splits), by_patch.records.shape[1])
+        for r in range(len(splits)):
+            bad = np.flatnonzero(a[r].view(np.uint32) != b[r].view(np.uint32))
+            assert bad.size == 0, "%s max_value %g shards %r rank %d: %d of %d record floats differ, first at %d" % (
+                name, max_value, splits, r, bad.size, a.shape[1], bad[0])
+        if len(splits) == 2:                                  # (and the shards differ: no rank trained on another's patches)
+            assert not np.array_equal(a[0], a[1])
+
+
+def test_world_of_one_through_patches_reproduces_train_step_patches_bit_for_bit():
+    """3 clipped adam steps with dropout: train_step_patches on one handle, local_gradients_patches + apply_records(world = 1) on
+    another.  Test A's property for the entry point train.py uses."""
+    _, weights = _net(X2)
+    d, patches, _ = _set14_draw(2, 15, 255.0)
+    flags = dict(dropout_rate=0.8, clipping_norm=0.5)
+    with _engine(X2, **flags) as one, PatchRig(X2, [5], **flags) as rig:
+        ids = {}
+        for i in range(3):
+            batch = patches[5 * i:5 * i + 5]
+            want = one.train_step_patches(_descriptors(one, d, batch, ids), LR_SIZE, 1e-3, dropout_key=KEY + i)
+            rig.local_patches(d, batch, KEY + i)
+            got = rig.apply(1e-3)[0]
+            print("step %d: stats %r (clipping_norm 0.5)" % (i, want))
+            assert want[2] > 0.5                                              # the clip factor is < 1
+            assert np.array_equal(np.array(want).view(np.uint64), np.array(got).view(np.uint64)), (want, got)
+            _assert_same_bits(_state(one, weights), _state(rig.engines[0], weights))
+
+
+def test_shards_through_patches_give_the_gradient_of_the_whole_batch():
+    """Shards 3+2 from descriptors, reduced on rank 0, against the float64 restatement on the WHOLE batch's host arrays at the bars
+    of tests/test_train_surface_hip.py (gradients 1e-4 * max|g64|, losses 1e-6, norm 1e-4); keep 0.8, MSE.  Fails if both ranks
+    train on shard 0, if first_index is dropped, or if the shards are weighted 1 / world."""
+    from test_train_surface_hip import L2_DECAY, _compare
+    cfg, weights = _net(X2)
+    d, patches, (x, x2, y) = _set14_draw(2, 5, 255.0)
+    with PatchRig(X2, (3, 2), dropout_rate=0.8, l2_decay=L2_DECAY) as rig:
+        rig.local_patches(d, patches, KEY)
+        stats = rig.apply(1e-3, which=[0])[0]
+        got = {k: rig.engines[0].get_tensor(k + "/grad") for k in weights}
+    _compare("patch route, shards 3+2 of 5 Set14 patches", cfg, weights, x, x2, y, stats, got, keep=0.8, key=KEY)
+
+
 # ---- F ------------------------------------------------------------------------------------------------------------------------
 
 NET_FLAGS = ["--scale=2", "--layers=7", "--filters=32", "--min_filters=8", "--filters_decay_gamma=1.2", "--nin_filters=24",
@@ -340,3 +438,61 @@ def test_train_py_with_two_and_three_ranks(tmp_path, one_process_steps, world, p
     assert m2, elog[-3000:]
     assert abs(float(m2.group(1)) - trained) < 1e-3, (trained, m2.group(1))
     assert np.isfinite(trained) and trained > 0.0
+
+
+# ---- H: SuperResolution.train_batch under a real process group, against the reference --------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _driver_reference():
+    """The batch tests/parallel_step_driver.py draws, drawn again on the host (load_batch_image), and the float64 restatement on
+    the WHOLE batch with the dropout key of step 0: computed once for the three worlds."""
+    import parallel_step_driver as D
+    from test_train_batches_hip import SET14, _draw
+    cfg, weights = _net(D.NET)
+    _, patches, (x, x2, y) = _draw(SET14, cfg["scale"], D.BATCH_IMAGE_SIZE, D.BATCH_NUM, seed=D.SEED, max_value=255.0)
+    ref, g64 = R.loss_and_grads(cfg, weights, x, x2, y, keep=D.FLAGS["dropout_rate"], key=0, l1=False, l2_decay=1e-4)
+    return patches, ref, g64
+
+
+@pytest.mark.parametrize("world,port", [(1, 0), (2, 29663), (3, 29664)])
+def test_model_step_under_a_process_group_against_the_reference(tmp_path, world, port):
+    """One gd step of SuperResolution (build_input_batch + train_batch) with `world` ranks sharing device 0 (gloo), as train.py
+    runs it, from a fixed draw seed: every rank's variables lie within lr * 1e-4 * max|g64| + one float32 ulp of max|w| of
+    w0 - lr * g64 (test D's bound, against the reference instead of a second run), the loss within 1e-6, all ranks hold the same
+    bits.  Every rank training on shard 0, first_index = 0 on every rank, or first_index lost on the patch route each move the
+    gradient by far more than that."""
+    import parallel_step_driver as D
+    patches, ref, g64 = _driver_reference()
+    _, weights = _net(D.NET)
+    env = dict(os.environ, DCSCN_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    script = os.path.join(ROOT, "tests", "parallel_step_driver.py")
+    cmd = [sys.executable]
+    if world > 1:
+        cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+                "--master-port", str(port)]
+    p = subprocess.run(cmd + [script, str(tmp_path)], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    log = p.stdout + p.stderr
+    assert p.returncode == 0, "\n".join(ln for ln in log.splitlines() if "Error" in ln)[-1500:] + "\n...\n" + log[-3000:]
+    ranks = [np.load(str(tmp_path / ("rank%d.npz" % r))) for r in range(world)]
+    worst = 0.0
+    for r, z in enumerate(ranks):
+        assert int(z["world"]) == world and int(z["key"]) == 0 and int(z["step"]) == 1 and float(z["max_value"]) == 255.0
+        assert float(z["l2_decay"]) == 1e-4 and float(z["lr"]) == D.LR
+        assert [(f, tuple(c)) for f, c in zip(z["files"], z["crops"].tolist())] == \
+            [(os.path.basename(f), (top, left, flip)) for f, top, left, flip in patches]      # the batch the reference was given
+        got = {str(n): z["t%d" % i] for i, n in enumerate(z["names"])}
+        assert set(got) == set(weights)
+        for k, w0 in weights.items():
+            want = w0.astype(np.float64) - D.LR * g64[k]
+            bound = D.LR * 1e-4 * float(np.max(np.abs(g64[k]))) + float(np.spacing(np.float32(np.max(np.abs(want)))))
+            err = float(np.max(np.abs(got[k].astype(np.float64) - want)))
+            moved = float(np.max(np.abs(got[k].astype(np.float64) - w0)))
+            worst = max(worst, err / bound)
+            print("world %d rank %d %-40s max |w - (w0 - lr g64)| %.3g  bound %.3g  (the step moved it by %.3g)" % (world, r, k, err, bound, moved))
+            assert err <= bound, (world, r, k, err, bound)
+            assert moved > 0.0
+            assert np.array_equal(got[k].view(np.uint32), ranks[0]["t%d" % list(ranks[0]["names"]).index(k)].view(np.uint32)), (r, k)
+        loss = float(z["training_loss_sum"])
+        assert abs(loss - ref["image_loss"]) <= 1e-6 * abs(ref["image_loss"]), (world, r, loss, ref)
+        assert loss == float(ranks[0]["training_loss_sum"])
+    print("world %d: worst error / bound %.3g, image loss %.17g (reference %.17g)" % (world, worst, float(ranks[0]["training_loss_sum"]), ref["image_loss"]))

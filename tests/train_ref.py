@@ -122,3 +122,120 @@ def momentum(w, g, a, lr, mu):
 
 def gd(w, g, lr):
     return w - lr * g
+
+
+# ---- dcscn_train_apply_records, restated operation by operation (include/dcscn.h "Data-parallel training") --------------------
+# train.hip is compiled with fp contract(off): every multiply, add, divide and sqrt below is one IEEE operation with one rounding,
+# in the order the kernels take them, so numpy float64 / float32 give the device's bits.
+
+RECORD_TRAILER_FLOATS = 8
+NORM_BLOCKS = 256                  # tsumsq's grid for the gradient norm (kNormBlocks)
+# make_records seed per variable count, chosen so that reducing a world of 8 in reversed rank order changes at least one float32 bit
+# of g (with and without the large values) and every one of the three float64 stats, and that summing its fractional counts from
+# the last rank changes a weight: the float64 sum hides the order in g unless it lands next to a float32 rounding boundary
+# (tests/test_train_parallel_host.py asserts all of it for each of them)
+RECORD_SEEDS = {2604: 360, 27209: 18, 28654: 42, 1823: 1186}
+
+
+def record_pad(count):
+    return (count + 3) // 4 * 4
+
+
+def make_records(count, world, seed, large=False, fractional=False, pad_value=12345.0):
+    """[world, record_floats] float32 records filled on the host: gradients N(0,1) * 10^U(-6, 2) of mixed sign with a few planted
+    elements (+-0, float32 subnormals, a pair that cancels across ranks 0 and 1, and with ``large`` values near the float32
+    maximum whose weighted sum stays finite), uneven positive integer patch counts, random positive doubles in trailer slots
+    0, 1 and 3, and ``pad_value`` (not zero) in the padding floats behind the gradient.  ``fractional`` scales every count by a
+    random factor: integers this small add up exactly in any order, so only such counts show the order the counts are summed in."""
+    rng = np.random.default_rng(seed)
+    pad = record_pad(count)
+    rec = np.full((world, pad + RECORD_TRAILER_FLOATS), pad_value, np.float32)
+    g = (rng.standard_normal((world, count)) * 10.0 ** rng.uniform(-6.0, 2.0, (world, count))).astype(np.float32)
+    sign = np.where(np.arange(world) % 2 == 0, 1.0, -1.0).astype(np.float32)
+    e = np.sort(rng.choice(count, 8, replace=False))             # where the planted elements sit: anywhere in the record
+    g[:, e[0]] = 0.0
+    g[:, e[1]] = -0.0
+    g[:, e[2]] = 0.0 * sign                                       # +0 and -0 mixed over the ranks
+    g[:, e[3]] = np.float32(1e-45) * sign                         # the smallest float32 subnormal
+    g[:, e[4]] = np.float32(3e-39)                                # subnormal on every rank
+    g[:, e[5]] = 0.0
+    g[0, e[5]] = 1.0
+    if world > 1:
+        g[1, e[5]] = np.float32(-1.0) + np.float32(2.0 ** -23)    # cancels against rank 0 down to the last bit, under unequal weights
+    if large:
+        g[:, e[6]] = np.float32(2.0e38)                           # a plain float32 sum overflows from world = 2 on; the weighted mean does not
+        g[:, e[7]] = np.float32(1.5e38) * sign                    # (and the norm of both, 2.5e38, is still a float32)
+    rec[:, :count] = g
+    counts = np.array(([3, 2, 2, 1] + [int(v) for v in rng.integers(1, 6, max(world - 4, 0))])[:world], np.float64)
+    tr = rng.uniform(0.5, 2000.0, (world, 4))
+    if fractional:
+        counts = counts * np.random.default_rng([seed, 1]).uniform(0.5, 1.5, world)
+    tr[:, 2] = counts
+    rec[:, pad:] = tr.view(np.float32)
+    return rec
+
+
+def record_parts(rec, count):
+    """(gradients [world, count] float32, trailers [world, 4] float64) of records."""
+    pad = record_pad(count)
+    return rec[:, :count], np.ascontiguousarray(rec[:, pad:]).view(np.float64)
+
+
+def rank_weights(counts, order=None):
+    """w_r = n_r / sum n_r, the sum taken in rank order (trank_weights)."""
+    counts = np.asarray(counts, np.float64)
+    total = np.float64(0.0)
+    for r in (range(len(counts)) if order is None else order):
+        total = total + counts[r]
+    return counts / total
+
+
+def weighted_sum(values, w, order=None):
+    """acc = w_0 * v_0, then acc = acc + w_r * v_r for r ascending, in float64 (treduce_ranks, tstats_ranks); ``order`` replaces
+    the rank order (the host tests use it to show that the order is visible in the result)."""
+    order = list(range(len(w))) if order is None else list(order)
+    acc = w[order[0]] * np.asarray(values[order[0]], np.float64)
+    for r in order[1:]:
+        acc = acc + w[r] * np.asarray(values[r], np.float64)
+    return acc
+
+
+def _tree(r):
+    """The LDS tree r[t] += r[t + o], o = 128 ... 1, over the last axis (256 wide); returns r[..., 0]."""
+    r = np.array(r, np.float64)
+    o = 128
+    while o > 0:
+        r[..., :o] = r[..., :o] + r[..., o:2 * o]
+        o //= 2
+    return r[..., 0]
+
+
+def tree_sumsq(g):
+    """Sum of squares of the float32 vector ``g`` in tsumsq's and tstats_ranks' order, as float64: NORM_BLOCKS blocks of
+    chunk = ceil(count / NORM_BLOCKS) elements, thread t of a block adds the squares of elements t, t + 256, ... of its chunk
+    in order, an LDS tree per block, then thread t of one block holds partial t and the same tree runs once more."""
+    g = np.asarray(g, np.float32).ravel()
+    count = g.size
+    chunk = (count + NORM_BLOCKS - 1) // NORM_BLOCKS
+    rows = (chunk + 255) // 256
+    sq = g.astype(np.float64) * g.astype(np.float64)
+    s = np.zeros((NORM_BLOCKS, 256), np.float64)
+    base = np.arange(NORM_BLOCKS, dtype=np.int64)[:, None] * chunk
+    for row in range(rows):
+        inside = row * 256 + np.arange(256, dtype=np.int64)[None, :]
+        idx = base + inside
+        valid = (inside < chunk) & (idx < count)
+        s = np.where(valid, s + sq[np.minimum(idx, count - 1)], s)
+    return _tree(0.0 + _tree(s))
+
+
+def reduce_records(rec, count, clipping_norm):
+    """(g float32 [count], stats: [image_loss, mse, float32 norm, total loss], float32 clip factor) of dcscn_train_apply_records."""
+    grads, tr = record_parts(rec, count)
+    w = rank_weights(tr[:, 2])
+    g = weighted_sum(grads, w).astype(np.float32)
+    norm = np.float32(np.sqrt(tree_sumsq(g)))
+    c = np.float32(clipping_norm)
+    clip = c / max(norm, c) if clipping_norm > 0 else np.float32(1.0)
+    stats = [weighted_sum(tr[:, 0], w), weighted_sum(tr[:, 1], w), norm, weighted_sum(tr[:, 3], w)]
+    return g, stats, np.float32(clip)
