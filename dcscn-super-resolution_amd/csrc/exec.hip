@@ -115,6 +115,16 @@ const char* kernel_name(Kernel k) {
     return names[k];
 }
 
+// whether the launch, or one of the launches it stands for where it runs layer by layer, takes a split16 kernel (option split16 = 3 keeps
+// the 1x1 GEMMs of a streamed launch's layers on conv_nin_h): the pass then needs its flags cleared and its float32 plan
+static bool op_any_split16(const dcscn_ctx* h, const Op& op) {
+    if (op_on_split16(h, op)) return true;
+    if (op_kernel(h, op, false) != K_LAYER_BY_LAYER) return false;
+    for (const Op& sub : op.fused)
+        if (op_any_split16(h, sub)) return true;
+    return false;
+}
+
 // what every launch of a pass shares.  redo = false: the launch of the pass (split16 kernels where the handle's options allow); true: the
 // op's float32 launch gated by the pass's redo flags -- only the images a split16 launch flagged are computed (run_pass)
 struct Pass {
@@ -547,7 +557,7 @@ static int run_pass(dcscn_ctx* h, const Pass& p) {
     const int nops = (int)h->ops.size(), s = h->cfg.scale;
     const size_t y_floats = (size_t)p.nb * p.H * s * p.W * s;
     bool any_h16 = false;
-    for (const Op& op : h->ops) any_h16 = any_h16 || op_on_split16(h, op);
+    for (const Op& op : h->ops) any_h16 = any_h16 || op_any_split16(h, op);
     if (any_h16)                                     // redo flags and the P16 planes' zero records
         HIP_TRY(h, pass_begin_launch(redo_flags(h), (int)h->redo_ints, h->p16_now ? h->d_zrec : nullptr, h->p16_now ? (int)h->h_zrec.size() : 0, p.stream));
     for (int i = 0; i < nops; ++i) {
