@@ -257,20 +257,20 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out) {
     out->executed_macs_per_lr_pixel = op.macs;
     if (op.kind == OP_FOLDX && h->finalized && s16) {
         out->nt = 1; out->kc = 32; out->n_tiles = 1;
-        out->executed_macs_per_lr_pixel = 3 * 25 * (int64_t)op.h16.n_chunks * 32 * 16;      // (the border ring's launch repeats 8 % of it on a 48 x 48 patch)
+        out->executed_macs_per_lr_pixel = (h->fast16 ? 1 : 3) * 25 * (int64_t)op.h16.n_chunks * 32 * 16;      // (the border ring's launch repeats 8 % of it on a 48 x 48 patch)
     }
     if (op.kind == OP_CONV && h->finalized) {
         out->mt = op.shape.mt; out->nt = op.shape.nt; out->kc = op.shape.kc; out->n_tiles = op.n_tiles;
         const int64_t r2 = (int64_t)op.res * op.res;
         const int64_t k_exec = (int64_t)op.n_chunks * op.shape.kc;             // padded input channels
         if (s16) {
-            // f16 multiply-accumulates issued: 3 products, input channels padded to 32, output channels to 16
+            // f16 multiply-accumulates issued: 3 products (1 with option "fast16"), input channels padded to 32, output channels to 16
             const int64_t tiles = (int64_t)op.h16.n_tiles * (op.h16.nt - 1) + op.h16.n_full;
             out->nt = op.h16.nt; out->kc = 32; out->n_tiles = op.h16.n_tiles;
             // MFMA steps of K = 32: 9 taps per chunk, 3 / 5 / 7 in a packed last chunk (conv3_h.hpp)
             const int64_t ksteps = op.shape.nin ? op.h16.n_chunks : op.fold_s > 0 ? 25 * (int64_t)op.h16.n_chunks
                                                 : 9 * (int64_t)(op.h16.n_chunks - (op.h16.tail_octs ? 1 : 0)) + (op.h16.tail_octs ? c3h_tail_steps(op.h16.tail_octs) : 0);
-            out->executed_macs_per_lr_pixel = r2 * 3 * ksteps * 32 * tiles * 16;
+            out->executed_macs_per_lr_pixel = r2 * (h->fast16 ? 1 : 3) * ksteps * 32 * tiles * 16;
         } else if (op.shape.nin) {
             const int64_t tiles = (int64_t)op.n_tiles * (op.shape.nt - 1) + op.n_full;
             out->executed_macs_per_lr_pixel = r2 * k_exec * tiles * 16;
@@ -350,6 +350,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
     if (!strcmp(key, "split16")) {                  // any time: the f16 images are always built, the option picks the launch
         h->split16 = value != 0;
         h->split16_mask = value == 2 ? 1 : value == 3 ? 2 : 3;
+        return DCSCN_OK;
+    }
+    if (!strcmp(key, "fast16")) {                   // any time: the same filter images and tensors, the option picks the instantiation (plan.h)
+        h->fast16 = value != 0;
         return DCSCN_OK;
     }
     if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)

@@ -107,7 +107,10 @@ static_assert(c3h_writes_conflict_free(), "c3h_unit: the two columns of an image
 // permutation on the source side, written to LDS as it is (ds_write_b128 at the lane-linear position), out-of-image pixels and octets past
 // the tensor's last read the plane's zero record: no conversion, no select, half the LDS store instructions.
 // Destinations may be P16 tensors (OutDesc::p16), each on its own: the epilogue then stores (hi | lo) units.
-template <int NT, int NTV, bool IN16 = false>
+// NP: products per MAC.  3 = the split16 contraction (wl * xh + wh * xl + wh * xh, f32 accuracy); 1 = option "fast16": wh * xh alone -- the
+// lo fragments are not read from LDS and their two MFMAs are not issued; staging, register arrays, barriers and the epilogue (which still
+// writes (hi | lo) units) are the three-product kernel's.
+template <int NT, int NTV, bool IN16 = false, int NP = 3>
 __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int tile_id, int ntile) {
     using G = C3HGeom<NT>;
     const int tid = threadIdx.x;
@@ -278,7 +281,7 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
         // The nine taps go column by column (step s: kx = s / 3, ky = s % 3): down a column the four pixel rows of the wave move
         // by one row per tap, so only ONE new row of B fragments is read per tap (rows ky .. ky + 3 live in xh / xl[(ky + m) & 3])
         // -- 12 row reads per column instead of 24; with the 2 NT filter fragments per tap that is 14 LDS reads per 12 NT MFMAs.
-        h8 xh[4], xl[4];
+        [[maybe_unused]] h8 xh[4], xl[4];
         static_for<0, 9>([&](auto s_) DCSCN_INL {
             constexpr int step = decltype(s_)::value;
             constexpr int kx = step / 3, ky = step % 3;
@@ -294,18 +297,21 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
             static_for<(ky == 0 ? 0 : 3), 4>([&](auto m_) DCSCN_INL {
                 constexpr int row = ky + decltype(m_)::value;
                 xh[row & 3] = *reinterpret_cast<const h8*>(smem + b_hi + row * G::ROW_BYTES);
-                xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
+                if constexpr (NP == 3) xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
             });
             const char* fs = smem + a_lane + slot * G::F_TAP_BYTES;
             static_for<0, NTV>([&](auto n_) DCSCN_INL {
                 constexpr int n = decltype(n_)::value;
                 const h8 wh = *reinterpret_cast<const h8*>(fs + (2 * n) * 1024);
-                const h8 wl = *reinterpret_cast<const h8*>(fs + (2 * n + 1) * 1024);
+                [[maybe_unused]] h8 wl;
+                if constexpr (NP == 3) wl = *reinterpret_cast<const h8*>(fs + (2 * n + 1) * 1024);
                 static_for<0, 4>([&](auto m_) DCSCN_INL {
                     constexpr int m = decltype(m_)::value;
                     constexpr int q = (ky + m) & 3;
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
+                    if constexpr (NP == 3) {
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
+                    }
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[q], acc[m][n], 0, 0, 0);
                 });
             });
@@ -339,21 +345,24 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
             const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
             const int hx = (l & 15) + kx;
             const int b = ((4 * wave + ky) * G::HT + hx) * G::PIX_BYTES + c3h_unit(hx, oct, 0) * 16;
-            h8 xh[4], xl[4];
+            [[maybe_unused]] h8 xh[4], xl[4];
             static_for<0, 4>([&](auto m_) DCSCN_INL {
                 constexpr int m = decltype(m_)::value;
                 xh[m] = *reinterpret_cast<const h8*>(smem + b + m * G::ROW_BYTES);
-                xl[m] = *reinterpret_cast<const h8*>(smem + (b ^ 16) + m * G::ROW_BYTES);
+                if constexpr (NP == 3) xl[m] = *reinterpret_cast<const h8*>(smem + (b ^ 16) + m * G::ROW_BYTES);
             });
             const char* fs = smem + a_lane + slot * G::F_TAP_BYTES;
             static_for<0, NTV>([&](auto n_) DCSCN_INL {
                 constexpr int n = decltype(n_)::value;
                 const h8 wh = *reinterpret_cast<const h8*>(fs + (2 * n) * 1024);
-                const h8 wl = *reinterpret_cast<const h8*>(fs + (2 * n + 1) * 1024);
+                [[maybe_unused]] h8 wl;
+                if constexpr (NP == 3) wl = *reinterpret_cast<const h8*>(fs + (2 * n + 1) * 1024);
                 static_for<0, 4>([&](auto m_) DCSCN_INL {
                     constexpr int m = decltype(m_)::value;
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[m], acc[m][n], 0, 0, 0);
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[m], acc[m][n], 0, 0, 0);
+                    if constexpr (NP == 3) {
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[m], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[m], acc[m][n], 0, 0, 0);
+                    }
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[m], acc[m][n], 0, 0, 0);
                 });
             });
@@ -577,7 +586,7 @@ __device__ __forceinline__ void conv3_h_body(const ConvArgs& a, char* smem, int 
 
 // 1-D grid decoded as conv_wino2's: the channel groups of one pixel tile get ids that are congruent mod 8 and close together
 // (same XCD, about the same time: the input tile is shared through that XCD's L2)
-template <int NT, int WPS = 2, bool IN16 = false>
+template <int NT, int WPS = 2, bool IN16 = false, int NP = 3>
 __global__ __launch_bounds__(256, WPS) void conv3_h(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_c3h[];
     const int Gn = a.n_groups, S = a.group_span;
@@ -592,8 +601,8 @@ __global__ __launch_bounds__(256, WPS) void conv3_h(const ConvArgs a) {
     const int ntile = phase * S + (r >> 3);
     const int tile_id = q * 8 + (r & 7);
     if (tile_id >= a.N * a.tiles_y * a.tiles_x) return;
-    if (ntile < a.n_full) conv3_h_body<NT, NT, IN16>(a, smem_c3h, tile_id, ntile);                 // block uniform
-    else if constexpr (NT >= 2) conv3_h_body<NT, NT - 1, IN16>(a, smem_c3h, tile_id, ntile);
+    if (ntile < a.n_full) conv3_h_body<NT, NT, IN16, NP>(a, smem_c3h, tile_id, ntile);                 // block uniform
+    else if constexpr (NT >= 2) conv3_h_body<NT, NT - 1, IN16, NP>(a, smem_c3h, tile_id, ntile);
 }
 
 }  // namespace dcscn

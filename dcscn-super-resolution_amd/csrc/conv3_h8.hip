@@ -10,9 +10,12 @@ static hipError_t c3e_set_attr() {
 
 hipError_t c3e16_init_kernels();                                // conv3_h8_p16.hip: P16 tensors in and out
 hipError_t c3e16_launch(int nt, const ConvArgs& a, int wgs, hipStream_t stream);
+hipError_t c3e1_init_kernels();                                 // conv3_h8_fast16.hip: one product per MAC (option "fast16"), float32 or P16 tensors
+hipError_t c3e1_launch(int nt, const ConvArgs& a, int wgs, bool p16, hipStream_t stream);
 
 hipError_t c3e_init_kernels() {
     hipError_t e = c3e16_init_kernels();
+    if (e == hipSuccess) e = c3e1_init_kernels();
     if (e != hipSuccess) return e;
     e = c3e_set_attr<6, 6>();
     if (e == hipSuccess) e = c3e_set_attr<6, 5>();
@@ -35,7 +38,7 @@ static hipError_t c3e_launch_one(const ConvArgs& a, int wgs, hipStream_t stream)
     return hipGetLastError();
 }
 
-hipError_t c3e_launch(int nt, const ConvArgs& args, int n_groups, int n_cus, hipStream_t stream) {
+hipError_t c3e_launch(int nt, const ConvArgs& args, int n_groups, int n_cus, hipStream_t stream, bool fast16) {
     if (!c3e_eligible(nt, args, n_groups) || !args.wpack16 || args.tiles_x != (args.W + 15) / 16 || args.tiles_y != (args.H + 15) / 16) return hipErrorInvalidValue;
     ConvArgs a = args;
     a.n_groups = n_groups;
@@ -45,8 +48,9 @@ hipError_t c3e_launch(int nt, const ConvArgs& args, int n_groups, int n_cus, hip
     const int wgs = (int)(units < n_cus ? units : n_cus);                 // one persistent workgroup per CU
     // P16 in and out (p16.hpp): the variant that stages its image by LDS-DMA; float32 in and out: the r04 kernel; anything mixed is not ours
     const bool out16 = a.out0.p16.base != nullptr && (a.split >= (1 << 29) || a.out1.p16.base != nullptr);
-    if (a.in16.base && out16) return c3e16_launch(nt, a, wgs, stream);
+    if (a.in16.base && out16) return fast16 ? c3e1_launch(nt, a, wgs, true, stream) : c3e16_launch(nt, a, wgs, stream);
     if (a.in16.base || a.out0.p16.base || a.out1.p16.base) return hipErrorInvalidValue;
+    if (fast16) return c3e1_launch(nt, a, wgs, false, stream);
     const bool eq = a.n_full == 2;
     switch (nt) {
         case 6: return eq ? c3e_launch_one<6, 6>(a, wgs, stream) : c3e_launch_one<6, 5>(a, wgs, stream);

@@ -84,9 +84,12 @@ struct C3EGeom {
 // immediate offset), 0 = args.nt_pack (tuner: one group split between the halves)
 // P16 = the input is a pre-split tensor (a.in16, p16.hpp) staged by LDS-DMA, and the destinations are P16 tensors too (the layers this
 // kernel runs feed split16 consumers only); false = float32 NHWC in and out, split in registers (r04)
-template <int NT, int C1, int NTP = NT, bool P16 = false>
+// NP = products per MAC (conv3_h.hpp): 3 = split16; 1 = option "fast16" -- the lo fragments (xl, wa) are not read and their MFMAs not issued,
+// everything else (DMA, vmcnt bookkeeping, barriers, register arrays, epilogue) is the three-product kernel's
+template <int NT, int C1, int NTP = NT, bool P16 = false, int NP = 3>
 __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     static_assert(C1 == NT || C1 == NT - 1, "half 1 takes as many tiles as half 0 or one fewer");
+    static_assert(NP == 1 || NP == 3, "one product (fast16) or three (split16)");
     // A fragments are read PFD channel tiles ahead of their MFMAs (the first PFD tiles in the load phase)
     constexpr int PFD = 2 < NT ? 2 : (NT > 1 ? NT - 1 : 1), NB = PFD + 1;
     using G = C3EGeom<NT>;
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     if (half == 1) asm volatile("s_setprio 1");                // half 1 runs at priority 1 for the whole kernel (see the header)
 
     f32x4 acc[4][NT];
-    h8 xh[4], xl[4], wa[NB], wb[NB];                           // B rows (hi, lo), A fragments (wl, wh) in a ring of PFD + 1 tiles
+    [[maybe_unused]] h8 xh[4], xl[4], wa[NB], wb[NB];                           // B rows (hi, lo), A fragments (wl, wh) in a ring of PFD + 1 tiles
     bool pending = false;                                      // an epilogue is owed (previous item)
     int parity = 0;
     // epilogue state of the previous item (its accumulators are still in acc until the first compute phase of the next item)
@@ -475,13 +478,13 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                 static_for<(ky == 0 ? 0 : 3), 4>([&](auto m_) DCSCN_INL {
                     constexpr int row = ky + decltype(m_)::value;
                     xh[row & 3] = *reinterpret_cast<const h8*>(smem + b_hi + row * G::ROW_BYTES);
-                    xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
+                    if constexpr (NP == 3) xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
                 });
                 const char* fs = smem + (step % 3 == 0 ? sl0 : step % 3 == 1 ? sl1 : sl2) + a_lane;
                 static_for<0, PFD>([&](auto p_) DCSCN_INL {
                     constexpr int p = decltype(p_)::value;
                     wb[p] = *reinterpret_cast<const h8*>(fs + (2 * p) * 1024);       // (tiles past the half's last: stale bytes of its own slot, never used)
-                    wa[p] = *reinterpret_cast<const h8*>(fs + (2 * p + 1) * 1024);
+                    if constexpr (NP == 3) wa[p] = *reinterpret_cast<const h8*>(fs + (2 * p + 1) * 1024);
                 });
                 auto dma_ahead = [&]() DCSCN_INL {   // the tap two steps ahead: of this chunk, of the next one, of the packed tail, or of the next item
                     constexpr int step2 = (step + 2) % 9;
@@ -520,10 +523,12 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                         constexpr int n = decltype(n_)::value;
                         if constexpr (n + PFD < CNT) {
                             wb[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD)) * 1024);
-                            wa[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD) + 1) * 1024);
+                            if constexpr (NP == 3) wa[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD) + 1) * 1024);
                         }
+                        if constexpr (NP == 3) {
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[n % NB], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xl[(ky + m) & 3], acc[m][n], 0, 0, 0); });
+                        }
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xh[(ky + m) & 3], acc[m][n], 0, 0, 0); });
                         __builtin_amdgcn_sched_barrier(0);     // a tile's reads and MFMAs stay where they are (hoisted, the reads of all tiles cost 40 more registers)
                     });
@@ -566,13 +571,13 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                 static_for<0, 4>([&](auto m_) DCSCN_INL {
                     constexpr int m = decltype(m_)::value;
                     xh[m] = *reinterpret_cast<const h8*>(smem + b + m * G::ROW_BYTES);
-                    xl[m] = *reinterpret_cast<const h8*>(smem + (b ^ 16) + m * G::ROW_BYTES);
+                    if constexpr (NP == 3) xl[m] = *reinterpret_cast<const h8*>(smem + (b ^ 16) + m * G::ROW_BYTES);
                 });
                 const char* fs = smem + sl0 + a_lane;
                 static_for<0, PFD>([&](auto p_) DCSCN_INL {
                     constexpr int p = decltype(p_)::value;
                     wb[p] = *reinterpret_cast<const h8*>(fs + (2 * p) * 1024);       // (tiles past the half's last: stale bytes of its own slot, never used)
-                    wa[p] = *reinterpret_cast<const h8*>(fs + (2 * p + 1) * 1024);
+                    if constexpr (NP == 3) wa[p] = *reinterpret_cast<const h8*>(fs + (2 * p + 1) * 1024);
                 });
                 if constexpr (DMA_LATE) {
                     if constexpr (P16) { if (!FIRST && step == 1) c3p_wait_vm<L>(); else c3p_wait_vm<0>(); }
@@ -586,10 +591,12 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
                         constexpr int n = decltype(n_)::value;
                         if constexpr (n + PFD < CNT) {
                             wb[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD)) * 1024);
-                            wa[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD) + 1) * 1024);
+                            if constexpr (NP == 3) wa[(n + PFD) % NB] = *reinterpret_cast<const h8*>(fs + (2 * (n + PFD) + 1) * 1024);
                         }
+                        if constexpr (NP == 3) {
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[n % NB], xh[m], acc[m][n], 0, 0, 0); });
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xl[m], acc[m][n], 0, 0, 0); });
+                        }
                         static_for<0, 4>([&](auto m_) DCSCN_INL { constexpr int m = decltype(m_)::value; acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[n % NB], xh[m], acc[m][n], 0, 0, 0); });
                         __builtin_amdgcn_sched_barrier(0);
                     });

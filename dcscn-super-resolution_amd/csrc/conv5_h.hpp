@@ -38,7 +38,8 @@ struct C5HGeom {
 };
 
 // IN16: the input is a P16 tensor (a.in16, p16.hpp), staged as in conv3_h<.., IN16>: one ready (hi | lo) unit per item, no conversion
-template <int NT, bool IN16 = false>
+// NP = products per MAC (conv3_h.hpp): 3 = split16; 1 = option "fast16": wh * xh alone, the lo fragments are not read from LDS
+template <int NT, bool IN16 = false, int NP = 3>
 __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv5_h(const ConvArgs a) {
     using G = C5HGeom<NT>;
     extern __shared__ __attribute__((aligned(16))) char smem_c5h[];
@@ -196,23 +197,26 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv5_h(const ConvArgs a
             if constexpr (kx == 0) load_in(nchunk);
             const int b_hi = b_col(std::integral_constant<int, kx>{});
             const char* fcol = smem + a_lane + slot * G::F_COL_BYTES;
-            h8 xh[4], xl[4];
+            [[maybe_unused]] h8 xh[4], xl[4];
             static_for<0, 5>([&](auto ky_) DCSCN_INL {
                 constexpr int ky = decltype(ky_)::value;
                 static_for<(ky == 0 ? 0 : 3), 4>([&](auto m_) DCSCN_INL {
                     constexpr int row = ky + decltype(m_)::value;
                     xh[row & 3] = *reinterpret_cast<const h8*>(smem + b_hi + row * G::ROW_BYTES);
-                    xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
+                    if constexpr (NP == 3) xl[row & 3] = *reinterpret_cast<const h8*>(smem + (b_hi ^ 16) + row * G::ROW_BYTES);
                 });
                 static_for<0, NT>([&](auto n_) DCSCN_INL {
                     constexpr int n = decltype(n_)::value;
                     const h8 wh = *reinterpret_cast<const h8*>(fcol + ky * G::F_TAP_BYTES + (2 * n) * 1024);
-                    const h8 wl = *reinterpret_cast<const h8*>(fcol + ky * G::F_TAP_BYTES + (2 * n + 1) * 1024);
+                    [[maybe_unused]] h8 wl;
+                    if constexpr (NP == 3) wl = *reinterpret_cast<const h8*>(fcol + ky * G::F_TAP_BYTES + (2 * n + 1) * 1024);
                     static_for<0, 4>([&](auto m_) DCSCN_INL {
                         constexpr int m = decltype(m_)::value;
                         constexpr int q = (ky + m) & 3;
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
+                        if constexpr (NP == 3) {
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[q], acc[m][n], 0, 0, 0);
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[q], acc[m][n], 0, 0, 0);
+                        }
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[q], acc[m][n], 0, 0, 0);
                     });
                 });
@@ -326,7 +330,7 @@ __host__ __device__ inline FoldBorderJobs fold_border_jobs(int N, int H, int W) 
     return j;
 }
 
-template <bool IN16>
+template <bool IN16, int NP = 3>
 __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_fb[];
     const int lane = threadIdx.x & 63;
@@ -423,12 +427,12 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
         // (and, corner jobs, 5 pixel fetches) are issued together, then the 15 MFMAs
 #pragma unroll
         for (int la = 0; la < 5; ++la) {
-            h8 wh[5], wl[5], xh[5], xl[5];
+            [[maybe_unused]] h8 wh[5], wl[5], xh[5], xl[5];
 #pragma unroll
             for (int sh = 0; sh < 5; ++sh) {
                 const int tap = along_x ? la * 5 + sh : sh * 5 + la;                 // (wave uniform)
                 wh[sh] = *reinterpret_cast<const h8*>(fc + tap * 2048);
-                wl[sh] = *reinterpret_cast<const h8*>(fc + tap * 2048 + 1024);
+                if constexpr (NP == 3) wl[sh] = *reinterpret_cast<const h8*>(fc + tap * 2048 + 1024);
             }
             if (corner) {
 #pragma unroll
@@ -440,13 +444,15 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
 #pragma unroll
                 for (int sh = 0; sh < 5; ++sh) {
                     xh[sh] = *reinterpret_cast<const h8*>(win + rd[sh] + la * (20 * 128));
-                    xl[sh] = *reinterpret_cast<const h8*>(win + (rd[sh] ^ 16) + la * (20 * 128));
+                    if constexpr (NP == 3) xl[sh] = *reinterpret_cast<const h8*>(win + (rd[sh] ^ 16) + la * (20 * 128));
                 }
             }
 #pragma unroll
             for (int sh = 0; sh < 5; ++sh) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[sh], xh[sh], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sh], xl[sh], acc, 0, 0, 0);
+                if constexpr (NP == 3) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[sh], xh[sh], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sh], xl[sh], acc, 0, 0, 0);
+                }
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[sh], xh[sh], acc, 0, 0, 0);
             }
         }

@@ -20,10 +20,13 @@ static hipError_t nin_h_set_attr() {
 
 hipError_t nin_h8_init_kernels();                                // conv_nin_h_w8.hip: 256 pixels per workgroup, for the wide K axes
 hipError_t nin_h8_launch(const ConvArgs& a, int n_groups, hipStream_t stream);
+hipError_t nin_h1_init_kernels();                                // conv_nin_h_fast16.hip: one product per MAC (option "fast16"), both workgroup sizes
+hipError_t nin_h1_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream);
 constexpr int kNinH8MinChunks = 32;                             // K >= 1024 channels (-3 % at 1301; slower at 540: profiles/r05_ninh_ablation.txt)
 
 hipError_t nin_h_init_kernels() {
     hipError_t e = nin_h8_init_kernels();
+    if (e == hipSuccess) e = nin_h1_init_kernels();
     if (e != hipSuccess) return e;
     e = nin_h_set_attr<1>();
     if (e == hipSuccess) e = nin_h_set_attr<2>();
@@ -52,9 +55,11 @@ static hipError_t nin_h_launch_one(const ConvArgs& a, int n_groups, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream) {
+hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream, bool fast16) {
     if (a.n_full < 1 || a.n_full > n_groups || (nt == 1 && a.n_full != n_groups) || !a.wpack16) return hipErrorInvalidValue;
-    if (w8 && nt == 6 && a.in16.base && a.n_chunks >= kNinH8MinChunks && a.n_full == n_groups) return nin_h8_launch(a, n_groups, stream);
+    const bool wide = w8 && nt == 6 && a.in16.base && a.n_chunks >= kNinH8MinChunks && a.n_full == n_groups;
+    if (fast16) return nin_h1_launch(nt, a, n_groups, wide, stream);
+    if (wide) return nin_h8_launch(a, n_groups, stream);
     switch (nt) {
         case 1: return nin_h_launch_one<1>(a, n_groups, stream);
         case 2: return nin_h_launch_one<2>(a, n_groups, stream);

@@ -47,7 +47,9 @@ struct NinHGeom {
 // SRC: 0 = one float32 tensor, 1 = MULTI (float32 sources through a per-quad table), 2 = P16 sources (p16.hpp) through a per-OCTET table:
 // entry = {address of the octet's hi unit in the record of pixel 0, record bytes}; the staged slot is then a ready (hi | lo) unit -- the B
 // fragments are read as they are, no split in registers.  Entries past the last octet point at a plane's zero record with stride 0.
-template <int NT, int NTV, int SRC, int S, int WAVES, int MT>
+// NP = products per MAC (conv3_h.hpp): 3 = split16; 1 = option "fast16": wh * xh alone -- the lo filter fragments and, with P16 sources, the
+// lo units of the input are not read from LDS (float32 sources are split in registers: their lo pieces are simply never computed)
+template <int NT, int NTV, int SRC, int S, int WAVES, int MT, int NP>
 __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, long long pix0, int ntile) {
     using G = NinHGeom<NT, S, WAVES, MT>;
     constexpr bool MULTI = SRC != 0, IN16 = SRC == 2;
@@ -135,11 +137,12 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
     });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    f32x4 xa[G::MT], xb[G::MT];
+    constexpr bool READ_B = NP == 3 || !IN16;                  // the second unit of a B fragment: the lo piece (IN16) or channels 4 .. 7 (float32)
+    [[maybe_unused]] f32x4 xa[G::MT], xb[G::MT];
     static_for<0, G::MT>([&](auto m_) DCSCN_INL {
         constexpr int m = decltype(m_)::value;
         xa[m] = *(lds_f32x4_ptr)(uintptr_t)(a_lane + m * 16 * G::PSTRIDE);
-        xb[m] = *(lds_f32x4_ptr)(uintptr_t)(a_lane2 + m * 16 * G::PSTRIDE);
+        if constexpr (READ_B) xb[m] = *(lds_f32x4_ptr)(uintptr_t)(a_lane2 + m * 16 * G::PSTRIDE);
     });
     __syncthreads();                                          // every wave holds its fragments of chunk 0: input stage 0 may be refilled
     unsigned sa = 0;                                          // chunk % S
@@ -152,18 +155,20 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
         const unsigned An = a_lane + sn * G::A_BYTES, An2 = a_lane2 + sn * G::A_BYTES;
         // filters first, then input: the counted wait below relies on this order
         static_for<0, G::B_ROUNDS>([&](auto r_) DCSCN_INL { dma_b(r_, cb, sb ^ 1); });
-        f32x4 na[G::MT], nb[G::MT];
+        [[maybe_unused]] f32x4 na[G::MT], nb[G::MT];
         static_for<0, G::MT>([&](auto m_) DCSCN_INL {
             constexpr int m = decltype(m_)::value;
-            h8 xh, xl;
-            if constexpr (IN16) { xh = __builtin_bit_cast(h8, xa[m]); xl = __builtin_bit_cast(h8, xb[m]); }
+            [[maybe_unused]] h8 xh, xl;
+            if constexpr (IN16) { xh = __builtin_bit_cast(h8, xa[m]); if constexpr (NP == 3) xl = __builtin_bit_cast(h8, xb[m]); }
             else split8(xa[m], xb[m], m1, xh, xl);
             static_for<0, NTV>([&](auto n_) DCSCN_INL {
                 constexpr int n = decltype(n_)::value;
                 const h8 wh = *(lds_h8_ptr)(uintptr_t)(Bs + (2 * n) * 1024);
-                const h8 wl = *(lds_h8_ptr)(uintptr_t)(Bs + (2 * n + 1) * 1024);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc[m][n], 0, 0, 0);
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc[m][n], 0, 0, 0);
+                if constexpr (NP == 3) {
+                    const h8 wl = *(lds_h8_ptr)(uintptr_t)(Bs + (2 * n + 1) * 1024);
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc[m][n], 0, 0, 0);
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc[m][n], 0, 0, 0);
+                }
                 acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc[m][n], 0, 0, 0);
                 // the chunk's input pieces behind the first MFMA groups
                 if constexpr (m * NTV + n < G::A_ROUNDS) dma_a(std::integral_constant<int, m * NTV + n>{}, ca, sa);
@@ -171,7 +176,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
             if constexpr (m == G::MT - 1 && G::MT * NTV < G::A_ROUNDS)
                 static_for<G::MT * NTV, G::A_ROUNDS>([&](auto r_) DCSCN_INL { dma_a(r_, ca, sa); });
             na[m] = *(lds_f32x4_ptr)(uintptr_t)(An + m * 16 * G::PSTRIDE);
-            nb[m] = *(lds_f32x4_ptr)(uintptr_t)(An2 + m * 16 * G::PSTRIDE);
+            if constexpr (READ_B) nb[m] = *(lds_f32x4_ptr)(uintptr_t)(An2 + m * 16 * G::PSTRIDE);
         });
         load_ent(chunk + S + 1 < last ? chunk + S + 1 : last);      // the next iteration's ca
         // the next chunk reads the fragments of chunk c + 2 and the filters of chunk c + 1: with S = 3 only this iteration's
@@ -179,7 +184,7 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
         if constexpr (S == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::A_ROUNDS) : "memory");
         __syncthreads();
-        static_for<0, G::MT>([&](auto m_) DCSCN_INL { xa[decltype(m_)::value] = na[decltype(m_)::value]; xb[decltype(m_)::value] = nb[decltype(m_)::value]; });
+        static_for<0, G::MT>([&](auto m_) DCSCN_INL { xa[decltype(m_)::value] = na[decltype(m_)::value]; if constexpr (READ_B) xb[decltype(m_)::value] = nb[decltype(m_)::value]; });
         sa = sn;
     }
     if constexpr (S > 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -261,13 +266,13 @@ __device__ __forceinline__ void conv_nin_h_body(const ConvArgs& a, float* smem, 
 }
 
 // grid = (pixel blocks of NinHGeom::PIX, channel groups)
-template <int NT, int SRC = 0, int S = 2, int WPS = 2, int WAVES = 4, int MT = 2>
+template <int NT, int SRC = 0, int S = 2, int WPS = 2, int WAVES = 4, int MT = 2, int NP = 3>
 __global__ __launch_bounds__(64 * WAVES, (WPS * WAVES / 4) * 128 / (16 * MT * WAVES) > 0 ? (WPS * WAVES / 4) * 128 / (16 * MT * WAVES) : 1) void conv_nin_h(const ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const long long pix0 = (long long)blockIdx.x * NinHGeom<NT, S, WAVES, MT>::PIX;
     const int ntile = blockIdx.y;
-    if (ntile < a.n_full) conv_nin_h_body<NT, NT, SRC, S, WAVES, MT>(a, smem, pix0, ntile);          // block uniform
-    else if constexpr (NT >= 2) conv_nin_h_body<NT, NT - 1, SRC, S, WAVES, MT>(a, smem, pix0, ntile);
+    if (ntile < a.n_full) conv_nin_h_body<NT, NT, SRC, S, WAVES, MT, NP>(a, smem, pix0, ntile);          // block uniform
+    else if constexpr (NT >= 2) conv_nin_h_body<NT, NT - 1, SRC, S, WAVES, MT, NP>(a, smem, pix0, ntile);
 }
 
 }  // namespace dcscn

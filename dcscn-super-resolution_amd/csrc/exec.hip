@@ -207,8 +207,8 @@ static int launch_foldx(dcscn_ctx* h, const Op& op, const Pass& p) {
     b.res = p.x2; b.res_stride = 1;
     b.fold = 2;
     b.redo = redo_flags(h);
-    HIP_TRY(h, c5h_launch(1, b, p.stream));
-    HIP_TRY(h, c5h_border_launch(b, p.stream));
+    HIP_TRY(h, c5h_launch(1, b, p.stream, h->fast16));
+    HIP_TRY(h, c5h_border_launch(b, p.stream, h->fast16));
     return DCSCN_OK;
 }
 
@@ -350,17 +350,17 @@ static int launch_conv(dcscn_ctx* h, const Op& op, const Pass& p, Kernel kernel)
     if (op.out_buf[0] >= 0 && h->bufs[op.out_buf[0]].p16) b.out0.p16 = p16_desc(h, op.out_buf[0]);
     if (op.out_buf[1] >= 0 && h->bufs[op.out_buf[1]].p16) b.out1.p16 = p16_desc(h, op.out_buf[1]);
     if (kernel == K_CONV_NIN_H) {
-        HIP_TRY(h, nin_h_launch(op.h16.nt, b, op.h16.n_tiles, h->nin_h8, p.stream));
+        HIP_TRY(h, nin_h_launch(op.h16.nt, b, op.h16.n_tiles, h->nin_h8, p.stream, h->fast16));
     } else if (kernel == K_CONV5_H) {
         b.bias = op.h16.d_bias;
-        HIP_TRY(h, c5h_launch(op.h16.nt, b, p.stream));
+        HIP_TRY(h, c5h_launch(op.h16.nt, b, p.stream, h->fast16));
     } else {
         b.bias = op.h16.d_bias;
         b.tail_octs = op.h16.tail_octs;
         b.alpha = op.h16.d_alpha;
         b.tiles_y = (Hr + 15) / 16;                           // (16 x 16 pixel tiles whatever the float32 kernel behind the layer uses)
-        if (kernel == K_CONV3_H8) HIP_TRY(h, c3e_launch(op.h16.nt, b, op.h16.n_tiles, h->n_cus, p.stream));
-        else HIP_TRY(h, c3h_launch(op.h16.nt, b, op.h16.n_tiles, p.stream));
+        if (kernel == K_CONV3_H8) HIP_TRY(h, c3e_launch(op.h16.nt, b, op.h16.n_tiles, h->n_cus, p.stream, h->fast16));
+        else HIP_TRY(h, c3h_launch(op.h16.nt, b, op.h16.n_tiles, p.stream, h->fast16));
     }
     return DCSCN_OK;
 }
@@ -661,6 +661,7 @@ int run_forward(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, 
     dcscn_ctx::GraphKey gkey;
     gkey.x = x; gkey.x2 = x2; gkey.y = y; gkey.stream = stream; gkey.n = n; gkey.H = H; gkey.W = W;
     gkey.split16 = h->split16 ? h->split16_mask : 0;
+    gkey.fast16 = h->split16 && h->fast16 ? 1 : 0;       // (picks the instantiation of every layer-kernel launch)
     gkey.nb = nb;                                        // the pass size (sub_batch_pixels / budget) shapes the launch sequence too
     gkey.h8 = h->conv3_h8 ? 1 : 0;
     gkey.nin_h8 = h->nin_h8 ? 1 : 0;

@@ -131,7 +131,8 @@ hipError_t nin_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t strea
 constexpr int kNinHKC = 32;
 hipError_t nin_h_init_kernels();
 // w8 (option "nin_h8"): launches with P16 sources, six tiles, every group full and K >= 1024 take 256-pixel workgroups (conv_nin_h_w8.hip)
-hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream);
+// fast16 (option "fast16", here and in the launchers below): the one-product instantiation (conv3_h.hpp: NP = 1) on the same arguments
+hipError_t nin_h_launch(int nt, const ConvArgs& a, int n_groups, bool w8, hipStream_t stream, bool fast16 = false);
 // conv3_h.hpp: 3x3 conv + bias + activator (+ depth_to_space) as a direct implicit GEMM; `nt` tiles per group (1..5), groups as for
 // wino_launch; args.wpack16 = pack_conv16 image with 9 taps, args.n_chunks = ceil(cin_phys / 32), args.redo (one flag per 16x16 tile)
 constexpr int kC3hKC = 32;
@@ -145,20 +146,20 @@ inline int c3h_tail_octs(int cin_phys) {
 }
 inline int c3h_tail_steps(int octs) { return (9 * octs + 3) / 4; }
 hipError_t c3h_init_kernels();
-hipError_t c3h_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream);
+hipError_t c3h_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream, bool fast16 = false);
 // conv3_h8 (conv3_h8.hpp): conv3_h's launches with exactly two channel groups as ONE persistent 8-wave workgroup per CU -- the pixel
 // tile's input image staged once for both groups, the halves running their load and compute parts in opposite order between one barrier per tap; same wpack16 image, same arguments, bit-identical results
 hipError_t c3e_init_kernels();
 bool c3e_eligible(int nt, const ConvArgs& a, int n_groups);
-hipError_t c3e_launch(int nt, const ConvArgs& a, int n_groups, int n_cus, hipStream_t stream);
+hipError_t c3e_launch(int nt, const ConvArgs& a, int n_groups, int n_cus, hipStream_t stream, bool fast16 = false);
 // conv5_h (conv5_h.hpp): the folded 5x5 tail on the f16 pipe; nt = ceil(4 ps^2 / 16) in {1, 3, 4}, one channel group, args as conv_launch's
 // fold launch plus args.wpack16 = pack_conv16 image with 25 taps, args.n_chunks = ceil(cin_phys / 32), args.inv_scale, args.redo
 hipError_t c5h_init_kernels();
-hipError_t c5h_launch(int nt, const ConvArgs& args, hipStream_t stream);
+hipError_t c5h_launch(int nt, const ConvArgs& args, hipStream_t stream, bool fast16 = false);
 // the border ring of a fold == 2 launch (conv5_h.hpp: fold_border): args.wpack16 = 16 pack_conv16 images [variant = 4 vy + vx][chunk][25 taps][hi | lo],
 // args.bias = [16 variants][16 phases]; vy / vx: 0 interior, 1 first row / column, 2 last, 3 both (a one-pixel axis)
 constexpr int kFoldVariants = 16;
-hipError_t c5h_border_launch(const ConvArgs& args, hipStream_t stream);
+hipError_t c5h_border_launch(const ConvArgs& args, hipStream_t stream, bool fast16 = false);
 
 // ---- row-streamed feature extractor of the separable narrow nets (feat_stream.hpp) ----
 constexpr int kStreamPX = 48;                  // computed columns per strip: three 16-pixel MFMA tiles

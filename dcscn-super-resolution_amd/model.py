@@ -90,6 +90,8 @@ class SuperResolution:
             self.psnr_calc_border_size = self.scale
         # extension: PSNR / SSIM of evaluated images on the device (csrc/metrics.hip) instead of numpy / scipy; off = the host code
         self.device_metrics = bool(getattr(flags, "device_metrics", False))
+        # extension: forwards take one f16 product per MAC (engine option "fast16"; set on every engine this model creates)
+        self.fast16 = bool(getattr(flags, "fast16", False))
 
         # training parameters (DCSCN.py:50-93)
         fget = lambda k, d: getattr(flags, k, d)
@@ -202,6 +204,8 @@ class SuperResolution:
         if self._engine is not None:
             self._engine.close()
         self._engine = engine.Engine(self._engine_config(), device=self.gpu_device_id)
+        if self.fast16:
+            self._engine.set_option("fast16", 1)
         self._weights = None
         return self._engine
 

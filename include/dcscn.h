@@ -219,6 +219,20 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * "nin_h8" (default 1; any time): the split16 1x1 GEMMs with K >= 1024 input channels, P16 sources and six full output tiles
  * (A1 || B1 of the L12 nets) run on 256-pixel workgroups of conv_nin_h -- half the filter traffic per pixel -- instead of 128-pixel
  * ones; same filter image, same products in the same order, bit-identical results.  0 = 128-pixel workgroups everywhere.
+ * "fast16" (default 0; any time, like "split16"): an opt-in LOWER-PRECISION inference mode.  With 1, every launch on conv3_h, conv3_h8
+ * (float32 or P16 tensors), conv_nin_h (both workgroup sizes) and conv5_h with fold_border -- the layer kernels of "split16" -- takes each
+ * contraction as the SINGLE product wh * xh: the activation rounded to f16, the weight (scaled by the layer's power of two) rounded to f16,
+ * the product exact and accumulated in f32.  The two products that carry the last 11 bits of each operand are not issued and their `lo`
+ * operands not read from LDS.  Everything else is split16's: the filter images and P16 records still hold (hi | lo) and epilogues still write
+ * both (a later fast16 = 0, or a launch that keeps three products, reads them as before), the 2^-e scale, bias, activators and the residual
+ * add run in f32, and the redo flags and the gated float32 plan work as described under "split16" -- a flagged image is still recomputed to
+ * the bits of a split16 = 0 run, bystanders keep their fast16 bits.  The streamed kernels (feat_stream, tail_stream, feat3_stream) keep
+ * three products, so the narrow nets change only in their folded tail; split16 = 0 ignores the option.
+ * Error against the float64 oracle on the 0-255 scale (seeded weights, U(0, 255) input), CPU model of the mode: max-abs 2.2e-3, rms 5.6e-4
+ * for L12 x2, 3.7e-3 / 9.4e-4 for L12 x4, 2.6e-3 / 8.3e-4 for L8 x2, 1.5e-3 / 4.4e-4 for c-DCSCN x2 -- about a hundred times split16's
+ * 1.5e-5 and 1/200 of an 8-bit step.  Measured on an MI355X: 2.3e-3 / 6.2e-4 (L12 x2), 3.1e-3 / 8.0e-4 (L12 x4), 3.5e-3 / 8.7e-4 (L8 x2);
+ * with the shipped c-DCSCN x2 weights, layer by layer, 1.3e-2 / 1.5e-3.  A 1024-patch pass of L12 x2 takes 0.667 of its time (DESIGN.md
+ * 3.13).  Not f32 accuracy, not bf16 / fp8, not for training.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The

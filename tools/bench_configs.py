@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Throughput of the other BASELINE.json configurations (bench.py measures configs[2]):
-   python tools/bench_configs.py [--steps 5]   -> one line per config, per-launch table with --ops."""
+   python tools/bench_configs.py [--steps 5]   -> one line per config, per-launch table with --ops.
+   --fast16: every config is timed with option fast16 = 0 and 1 ALTERNATING in one process (--rounds blocks of --steps passes each,
+   median block per setting), one line per setting plus their ratio; with --ops the per-launch times of both settings side by side."""
 import argparse
 import os
 import sys
@@ -23,12 +25,56 @@ CONFIGS = [
 ]
 
 
+def fast16_compare(args, name, eng, torch, io):
+    """fast16 = 0 and 1 in alternating blocks of args.steps passes on one handle; median block per setting."""
+    x, x2, y, n, st = io
+    run = lambda: eng.forward_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, 48, 48, st)
+    for v in (0, 1):                                   # warm both settings (and capture both graphs with --graph)
+        eng.set_option("fast16", v)
+        for _ in range(3):
+            run()
+    torch.cuda.synchronize()
+    times = {0: [], 1: []}
+    for _ in range(args.rounds):
+        for v in (0, 1):
+            eng.set_option("fast16", v)
+            run()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                run()
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0) / args.steps * 1e3)
+    med = {v: sorted(t)[len(t) // 2] for v, t in times.items()}
+    for v in (0, 1):
+        print("%-48s fast16 %d  %8.3f ms/step median of %d blocks (min %.3f max %.3f)" % (name, v, med[v], args.rounds, min(times[v]), max(times[v])), flush=True)
+    print("%-48s fast16 1 / fast16 0 = %.4f" % (name, med[1] / med[0]), flush=True)
+    if args.ops and not args.graph:
+        per = {}
+        eng.set_option("profile", 1)
+        for v in (0, 1):
+            eng.set_option("fast16", v)
+            rows = []
+            for _ in range(args.steps):
+                run()
+                torch.cuda.synchronize()
+                rows.append(eng.profile())
+            per[v] = [sorted(c)[len(c) // 2] for c in zip(*rows)]
+        eng.set_option("profile", 0)
+        for o, a, b in zip(eng.ops(), per[0], per[1]):
+            print("    %-26s %-11s k%d %4d->%-4d res%d  fast16 0 %8.3f ms  fast16 1 %8.3f ms  ratio %.3f" % (
+                o["name"], o["kernel"], o["kernel_size"], o["in_channels"], o["out_channels"], o["resolution"], a, b, b / a if a else 0))
+        print("    %-26s fast16 0 %8.3f ms  fast16 1 %8.3f ms" % ("sum of launches", sum(per[0]), sum(per[1])), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--ops", action="store_true")
     ap.add_argument("--only", default="")
     ap.add_argument("--graph", action="store_true", help="option graph_replay: the pass replayed from a hipGraph")
+    ap.add_argument("--fast16", action="store_true", help="time fast16 = 0 and 1 alternating in one process and print the ratio")
+    ap.add_argument("--rounds", type=int, default=7, help="--fast16: timed blocks per setting")
     args = ap.parse_args()
     import torch
     import dcscn_oracle as O
@@ -46,6 +92,10 @@ def main():
         st = torch.cuda.current_stream().cuda_stream
         if args.graph:
             eng.set_option("graph_replay", 1)
+        if args.fast16:
+            fast16_compare(args, name, eng, torch, (x, x2, y, n, st))
+            eng.close()
+            continue
         for _ in range(3):
             eng.forward_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, 48, 48, st)
         if not args.graph:

@@ -90,6 +90,16 @@ def gemm_f16x3(a, b, sa=None, sb=None, flush=False, acc=None):
     return out, 1.0 / (sa * sb)
 
 
+def gemm_f16x1(a, b, sa=None, sb=None, flush=False, acc=None):
+    """The hi pieces only (engine option "fast16"): one product per MAC, exact in f32, blocks of 32 added to an f32 accumulator."""
+    sa = pow2_scale(a, 2.0 ** 15) if sa is None else sa
+    sb = pow2_scale(b, 2.0 ** 15) if sb is None else sb
+    ah, _ = f16_split(a, sa, flush)
+    bh, _ = f16_split(b, sb, flush)
+    out = gemm_blocks([(ah, bh)], a.shape[1], None, acc, (a.shape[0], b.shape[1]))
+    return out, 1.0 / (sa * sb)
+
+
 def gemm_bf16(a, b, n_products):
     a1, a2, a3 = bf16_split3(a)
     b1, b2, b3 = bf16_split3(b)
@@ -128,6 +138,10 @@ def single_contractions():
         got, inv = gemm_f16x3(a, b, sa=1.0)
         report("f16 hi/lo, 3 products, act scale 1", got.astype(np.float64) * inv, truth)
         got, inv = gemm_f16x3(a, b, sa=1.0, flush=True)
+        report("  ... and flushed subnormals", got.astype(np.float64) * inv, truth)
+        got, inv = gemm_f16x1(a, b, sa=1.0)
+        report("f16 hi only, 1 product, act scale 1", got.astype(np.float64) * inv, truth)
+        got, inv = gemm_f16x1(a, b, sa=1.0, flush=True)
         report("  ... and flushed subnormals", got.astype(np.float64) * inv, truth)
         report("bf16 x 3 pieces, 6 products", gemm_bf16(a, b, 6), truth)
         report("bf16 x 3 pieces, 3 products", gemm_bf16(a, b, 3), truth)
@@ -175,6 +189,8 @@ class ConvModel:
                 a = xp[:, dy:dy + h, dx:dx + wd, :].reshape(-1, cin)
                 if self.mode == "f16x3":
                     acc, _ = gemm_f16x3(a, w[dy, dx], sa, sb, self.flush, acc)
+                elif self.mode == "f16x1":
+                    acc, _ = gemm_f16x1(a, w[dy, dx], sa, sb, self.flush, acc)
                 else:
                     raise ValueError(self.mode)
         return (acc.astype(np.float64) / (sa * sb)).astype(F32).reshape(n, h, wd, cout)
@@ -211,11 +227,13 @@ def chain():
                                 ("f16 hi/lo x3, fixed act scale 1", ConvModel("f16x3", act_scale=1.0)),
                                 ("f16 hi/lo x3, fixed act scale 16", ConvModel("f16x3", act_scale=16.0)),
                                 ("f16 hi/lo x3, scale 1, flush subnormals", ConvModel("f16x3", act_scale=1.0, flush=True)),
-                                ("f16 hi/lo x3, scale 16, flush subnormals", ConvModel("f16x3", act_scale=16.0, flush=True))):
+                                ("f16 hi/lo x3, scale 16, flush subnormals", ConvModel("f16x3", act_scale=16.0, flush=True)),
+                                ("f16 hi only x1 (fast16), act scale 1", ConvModel("f16x1", act_scale=1.0)),
+                                ("f16 hi only x1, scale 1, flush subnormals", ConvModel("f16x1", act_scale=1.0, flush=True))):
                 O.conv2d_same = model
                 y = O.forward(cfg, weights, x, xx2, dtype=F32)
                 e = np.abs(y.astype(np.float64) - truth)
-                print("    %-42s max-abs %.3g   relative to max|y| %.3g" % (name, e.max(), e.max() / np.abs(truth).max()))
+                print("    %-42s max-abs %.3g   rms %.3g   relative to max|y| %.3g" % (name, e.max(), np.sqrt((e ** 2).mean()), e.max() / np.abs(truth).max()))
                 results[(tag, name)] = e.max()
                 last = model
         finally:

@@ -1,5 +1,6 @@
 // Correctness + timing harness for the split16 kernels (f32-accurate contraction on the f16 matrix pipe) against the f32
-// kernels they stand in for and a float64 naive reference.
+// kernels they stand in for and a float64 naive reference; beside them the ONE-product forms of the same kernels (option "fast16": NP = 1,
+// wh * xh only), whose error against the float64 reference is printed, not judged (it is the f16 rounding of the operands).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize tools/h16_tune.hip -o tools/h16_tune
 //   tools/h16_tune nin      A1 || B1 of the bench model (1316 -> 96 over 1024 patches): conv_nin vs conv_nin_h, one tensor / 12 sources,
 //                           ragged pixel counts and channel tails, and the overflow -> redo -> f32 fallback path
@@ -229,7 +230,8 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
     const dim3 grid((unsigned)nblocks, (unsigned)ng);
     float ms32 = 0, ms16 = 0;
     const size_t tab_bytes = C.multi ? (size_t)n_chunks * 64 : 0;
-    auto launch = [&](auto nt_c, bool h16, float* outp, bool redo_check) {
+    // h16: 0 = the f32 kernel, 3 = conv_nin_h (three products), 1 = its one-product form
+    auto launch = [&](auto nt_c, int h16, float* outp, bool redo_check) {
         constexpr int NTc = decltype(nt_c)::value;
         ConvArgs b = a;
         b.out0 = OutDesc{outp, out_stride, 0, out_stride};
@@ -241,7 +243,11 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
             b.wpack16 = d_p16b; b.n_chunks = n_chunks32;
             const dim3 grid2((unsigned)((npix + 127) / 128), (unsigned)ng);
             const size_t tab2 = C.multi ? (size_t)n_chunks32 * 128 : 0;
-            if (g_S == 2) {
+            if (h16 == 1) {
+                const size_t lds = NinHGeom<NTc, 3>::LDS_BYTES + tab2;
+                if (C.multi) { auto k = conv_nin_h<NTc, 1, 3, 2, 4, 2, 1>; CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ms = time_kernel(k, grid2, lds, b, reps); }
+                else { auto k = conv_nin_h<NTc, 0, 3, 2, 4, 2, 1>; CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ms = time_kernel(k, grid2, lds, b, reps); }
+            } else if (g_S == 2) {
                 const size_t lds = NinHGeom<NTc, 2>::LDS_BYTES + tab2;
                 if (C.multi) { auto k = conv_nin_h<NTc, true, 2>; CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ms = time_kernel(k, grid2, lds, b, reps); }
                 else { auto k = conv_nin_h<NTc, false, 2>; CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ms = time_kernel(k, grid2, lds, b, reps); }
@@ -257,7 +263,7 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
         }
         return ms;
     };
-    auto dispatch = [&](bool h16, float* outp, bool redo_check) {
+    auto dispatch = [&](int h16, float* outp, bool redo_check) {
         switch (nt) {
             case 1: return launch(std::integral_constant<int, 1>{}, h16, outp, redo_check);
             case 2: return launch(std::integral_constant<int, 2>{}, h16, outp, redo_check);
@@ -267,8 +273,17 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
             default: return launch(std::integral_constant<int, 6>{}, h16, outp, redo_check);
         }
     };
-    ms32 = dispatch(false, d_o32, false);
-    ms16 = dispatch(true, d_o16, false);
+    ms32 = dispatch(0, d_o32, false);
+    // the one-product form first, into the split16 output buffer (read back below before the three-product launch overwrites it)
+    std::vector<float> o1;
+    float ms1 = 0;
+    if (!overflow_test) {
+        ms1 = dispatch(1, d_o16, false);
+        o1.resize((size_t)npix * out_stride);
+        CK(hipMemcpy(o1.data(), d_o16, o1.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemset(d_redo, 0, nblocks * 4));
+    }
+    ms16 = dispatch(3, d_o16, false);
     int bad = 0;
     std::vector<int> redo(nblocks);
     CK(hipMemcpy(redo.data(), d_redo, nblocks * 4, hipMemcpyDeviceToHost));
@@ -276,7 +291,7 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
     for (int v : redo) nflag += v != 0;
     if (overflow_test) {
         if (nflag != 1 || !redo[poke_pix / 256]) { printf("  ** redo flags wrong: %lld set, block of the poked pixel %d\n", nflag, redo[poke_pix / 256]); ++bad; }
-        dispatch(false, d_o16, true);          // the fallback launch: only the flagged block is recomputed (into the split16 output)
+        dispatch(0, d_o16, true);              // the fallback launch: only the flagged block is recomputed (into the split16 output)
     } else if (nflag) { printf("  ** %lld redo flags set without an overflow\n", nflag); ++bad; }
 
     std::vector<float> rf((size_t)npix * out_stride), o32(rf.size()), o16(rf.size());
@@ -305,6 +320,18 @@ static int run_nin(const NinCase& C, bool timing, int overflow_test) {
            C.name, npix, cin, cout, C.multi ? "multi " : "single", nt, ng, n_chunks, ms32, flop / ms32 * 1e-9, bytes / ms32 * 1e-9, ms16, flop / ms16 * 1e-9,
            bytes / ms16 * 1e-9, e32, e16, std::sqrt(s32 / cnt), std::sqrt(s16 / cnt), mx, d3216, ok ? "" : "  ** MISMATCH **");
     bad += !ok;
+    if (!o1.empty()) {
+        double e1 = 0, s1 = 0;
+        for (long long p = 0; p < npix; p += step)
+            for (int c = 0; c < cout; ++c) {
+                const size_t i = (size_t)p * out_stride + c;
+                const double a1 = std::fabs((double)o1[i] - rf[i]);
+                if (!(a1 <= e1)) e1 = a1;
+                s1 += a1 * a1;
+            }
+        printf("%-14s   one product (fast16): %7.3f ms (%.3f of f16x3)  max err %.3g  rms %.3g  (%.0f x the f16x3 rms)\n", C.name, ms1, ms1 / ms16, e1, std::sqrt(s1 / cnt),
+               std::sqrt(s1 / cnt) / std::sqrt(s16 / cnt));
+    }
     fflush(stdout);
     for (float* p : d_src) if (p) CK(hipFree(p));
     if (d_one) CK(hipFree(d_one));

@@ -178,6 +178,33 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NTc>::LDS_BYTES));
         return time_kernel(k, grid, C3HGeom<NTc>::LDS_BYTES, b, reps);
     };
+    // ---- the one-product form (option "fast16": NP = 1) first, into the same buffer; read back before the three-product launch overwrites it ----
+    std::vector<float> o1;
+    float ms1 = 0;
+    if (!overflow_test) {
+        auto run1 = [&](auto nt_c) {
+            constexpr int NTc = decltype(nt_c)::value;
+            auto k = conv3_h<NTc, 2, false, 1>;
+            CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, C3HGeom<NTc>::LDS_BYTES));
+            return time_kernel(k, grid, C3HGeom<NTc>::LDS_BYTES, b, reps);
+        };
+        switch (nt) {
+            case 1: ms1 = run1(std::integral_constant<int, 1>{}); break;
+            case 2: ms1 = run1(std::integral_constant<int, 2>{}); break;
+            case 3: ms1 = run1(std::integral_constant<int, 3>{}); break;
+            case 4: ms1 = run1(std::integral_constant<int, 4>{}); break;
+#if C3H_MAX_NT >= 5
+            case 5: ms1 = run1(std::integral_constant<int, 5>{}); break;
+#endif
+#if C3H_MAX_NT >= 6
+            case 6: ms1 = run1(std::integral_constant<int, 6>{}); break;
+#endif
+            default: printf("no conv3_h<%d>\n", nt); exit(1);
+        }
+        o1.resize((size_t)n_check * H * L.ps * W * L.ps * out_stride);
+        CK(hipMemcpy(o1.data(), d_o16, o1.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemset(d_redo, 0, n_tiles * 4));
+    }
     switch (nt) {
         case 1: r.ms16 = run16(std::integral_constant<int, 1>{}); break;
         case 2: r.ms16 = run16(std::integral_constant<int, 2>{}); break;
@@ -324,6 +351,17 @@ static R3 run_conv3(const Layer3& L, int N, int H, int W, int n_check, bool timi
                L.name, L.cin, L.cout, N, H, W, L.ps, nt32, r.ms32, flop / r.ms32 * 1e-9, nt, ng, nfull, n_chunks, r.ms16, flop / r.ms16 * 1e-9, r.mshp, flop / r.mshp * 1e-9,
                hp_diff ? "  ** hp != conv3_h **" : "", r.msh8, r.msh8 > 0 ? flop / r.msh8 * 1e-9 : 0.0, h8_diff ? "  ** h8 != conv3_h **" : "", r.e32, r.e16,
                std::sqrt(s32 / nn), std::sqrt(s16 / nn), r.maxv, ok ? "" : "  ** MISMATCH **", stray != 0 ? "  ** STRAY WRITE **" : "");
+    if (!o1.empty() && (!quiet || !ok || r.bad)) {
+        double e1 = 0, s1 = 0;
+        for (size_t px = 0; px < cnt / out_stride; ++px)
+            for (int c = 0; c < cstore; ++c) {
+                const double a1 = std::fabs((double)o1[px * out_stride + c] - rf[px * out_stride + c]);
+                if (!(a1 <= e1)) e1 = a1;
+                s1 += a1 * a1;
+            }
+        printf("%-8s   one product (fast16): %7.3f ms (%.3f of f16x3)  max err %.3g  rms %.3g  (%.0f x the f16x3 rms)\n", L.name, ms1, ms1 / r.ms16, e1, std::sqrt(s1 / nn),
+               std::sqrt(s1 / nn) / std::sqrt(s16 / nn));
+    }
     fflush(stdout);
     CK(hipFree(d_in)); CK(hipFree(d_ref)); CK(hipFree(d_o32)); CK(hipFree(d_o16)); CK(hipFree(d_wraw)); CK(hipFree(d_bias)); CK(hipFree(d_alpha));
     if (d_ohp) CK(hipFree(d_ohp)); if (d_work) CK(hipFree(d_work)); CK(hipFree(d_p32)); CK(hipFree(d_bp32)); CK(hipFree(d_ap32)); CK(hipFree(d_p16)); CK(hipFree(d_bp)); CK(hipFree(d_ap)); CK(hipFree(d_redo));
