@@ -15,10 +15,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_NAME = "libdcscn_hip.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
-SOURCES = ["api.hip", "graph.hip", "pack.hip", "exec.hip", "kernels.hip", "resample.hip", "ensemble.hip", "color.hip", "metrics.hip", "conv_k1.hip", "conv_k3.hip", "conv_k5.hip", "conv_k7.hip", "conv_wino2.hip", "conv_nin.hip", "feat_stream.hip", "conv_nin_h.hip", "conv_nin_h_w8.hip", "conv3_h.hip", "conv3_h8.hip", "conv5_h.hip", "conv3_h_p16.hip", "conv3_h8_p16.hip", "conv3_h_fast16.hip", "conv3_h8_fast16.hip", "conv_nin_h_fast16.hip", "conv5_h_fast16.hip", "feat_stream_redo.hip", "feat3_stream.hip", "train.hip", "train_data.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("kernels.h", "plan.h", "conv_igemm.hpp", "conv_wino2.hpp", "conv_nin.hpp", "conv_variants.hpp", "feat_stream.hpp", "tail_stream.hpp", "feat3_stream.hpp",
-                                              "split16.hpp", "split16_pack.hpp", "p16.hpp", "conv_nin_h.hpp", "conv3_h.hpp", "conv3_h8.hpp", "conv5_h.hpp")] + \
-          [os.path.join(INCLUDE, "dcscn.h")]
+HEADERS = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith((".h", ".hpp"))] + [os.path.join(INCLUDE, "dcscn.h")]
 ARCH = "gfx950"
 # No packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in any kernel: beside ANOTHER process's MFMA work on
 # the same SIMD their low-half results come back wrong in lanes 48-63 (tools/xproc_triage.hip: victim cin1p vs cin1s next to
@@ -26,13 +23,27 @@ ARCH = "gfx950"
 # passed to the host compilation as well, which reports it as unknown and ignores it (filtered from the output below).
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + NO_PK_F32
-# per-source extra flags (see the comment at the top of conv_wino2.hip)
-EXTRA_FLAGS = {"conv_wino2.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
-               "conv_nin.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"],
-               "conv_nin_h.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv_nin_h_w8.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h8.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h_p16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h8_p16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv5_h.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h_fast16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv3_h8_fast16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv_nin_h_fast16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "conv5_h_fast16.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "color.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "feat_stream.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"], "feat_stream_redo.hip": ["-fno-slp-vectorize"], "feat3_stream.hip": ["-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage"]}
-# kernels that sit at the VGPR limit by design (192 accumulators + operands): a register spill inside their K loop also
-# breaks the hand-counted vmcnt accounting of the LDS-DMA pipeline, so a build that spills is rejected, not shipped
-NO_SCRATCH = ("conv_wino2.hip", "conv_nin.hip", "feat_stream.hip", "conv_nin_h.hip", "conv_nin_h_w8.hip", "conv_nin_h_w8.hip", "conv3_h.hip", "conv3_h8.hip", "conv5_h.hip", "conv3_h_p16.hip", "conv3_h8_p16.hip", "conv3_h_fast16.hip", "conv3_h8_fast16.hip", "conv_nin_h_fast16.hip", "conv5_h_fast16.hip", "feat3_stream.hip")
+# -fno-slp-vectorize: see the comment at the top of conv_wino2.hip; the resource-usage remarks feed the spill gate of _run
+NO_SLP = ["-fno-slp-vectorize"]
+KERNEL = NO_SLP + ["-Rpass-analysis=kernel-resource-usage"]
+NO_CONTRACT = ["-ffp-contract=off"]
+# source: (extra flags, must not spill).  Must not spill: kernels that sit at the VGPR limit by design (192 accumulators + operands) -- a
+# register spill inside their K loop also breaks the hand-counted vmcnt accounting of the LDS-DMA pipeline, so a build that spills is
+# rejected, not shipped
+SOURCE_TABLE = {
+    "api.hip": ([], False), "graph.hip": ([], False), "pack.hip": ([], False), "exec.hip": ([], False), "kernels.hip": ([], False),
+    "resample.hip": ([], False), "ensemble.hip": ([], False), "color.hip": (NO_CONTRACT, False), "metrics.hip": (NO_CONTRACT, False),
+    "conv_k1.hip": ([], False), "conv_k3.hip": ([], False), "conv_k5.hip": ([], False), "conv_k7.hip": ([], False),
+    "conv_wino2.hip": (KERNEL, True), "conv_nin.hip": (KERNEL, True), "feat_stream.hip": (KERNEL, True),
+    "conv_nin_h.hip": (KERNEL, True), "conv_nin_h_w8.hip": (KERNEL, True), "conv3_h.hip": (KERNEL, True), "conv3_h8.hip": (KERNEL, True),
+    "conv5_h.hip": (KERNEL, True), "conv3_h_p16.hip": (KERNEL, True), "conv3_h8_p16.hip": (KERNEL, True),
+    "conv3_h_fast16.hip": (KERNEL, True), "conv3_h8_fast16.hip": (KERNEL, True), "conv_nin_h_fast16.hip": (KERNEL, True),
+    "conv5_h_fast16.hip": (KERNEL, True), "feat_stream_redo.hip": (NO_SLP, False), "feat3_stream.hip": (KERNEL, True),
+    "train.hip": ([], False), "train_data.hip": ([], False),
+}
+SOURCES = list(SOURCE_TABLE)
+EXTRA_FLAGS = {src: flags for src, (flags, _) in SOURCE_TABLE.items()}
+NO_SCRATCH = tuple(src for src, (_, no_spill) in SOURCE_TABLE.items() if no_spill)
 
 
 def hipcc_path():

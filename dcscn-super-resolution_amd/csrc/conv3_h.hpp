@@ -37,6 +37,7 @@
 #include "conv_wino2.hpp"
 #include "split16.hpp"
 #include "p16.hpp"
+#include "variant_list.hpp"
 
 namespace dcscn {
 
@@ -604,5 +605,33 @@ __global__ __launch_bounds__(256, WPS) void conv3_h(const ConvArgs a) {
     if (ntile < a.n_full) conv3_h_body<NT, NT, IN16, NP>(a, smem_c3h, tile_id, ntile);                 // block uniform
     else if constexpr (NT >= 2) conv3_h_body<NT, NT - 1, IN16, NP>(a, smem_c3h, tile_id, ntile);
 }
+
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation; arguments checked by c3h_launch ----
+constexpr int c3h_key(int nt, bool in16) { return 2 * nt + in16; }
+
+template <int NT, bool IN16, int NP>
+struct C3HVariant {
+    static constexpr int KEY = c3h_key(NT, IN16);
+    static constexpr auto kernel = &conv3_h<NT, 2, IN16, NP>;
+    static constexpr int THREADS = C3HGeom<NT>::THREADS, LDS = C3HGeom<NT>::LDS_BYTES;
+    static hipError_t set_attr() { return allow_lds(kernel, LDS); }
+    static hipError_t launch(ConvArgs a, int n_groups, hipStream_t stream) {
+        const long long ids = xcd_grid_ids(a, n_groups);
+        if (ids > 0x7fffffffLL || (IN16 && (long long)a.N * a.H * a.W > kP16MaxPixels)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)ids), dim3(THREADS), LDS, stream, a);
+        return hipGetLastError();
+    }
+};
+// every NT of one (input form, products per MAC)
+template <bool IN16, int NP>
+using C3HVariants = Variants<C3HVariant<1, IN16, NP>, C3HVariant<2, IN16, NP>, C3HVariant<3, IN16, NP>, C3HVariant<4, IN16, NP>, C3HVariant<5, IN16, NP>,
+                             C3HVariant<6, IN16, NP>>;
+static_assert(kC3hMaxNT == 6, "C3HVariants lists NT 1 .. kC3hMaxNT");
+
+// the translation units behind c3h_launch (key = c3h_key)
+hipError_t c3h16_init_kernels();                                // conv3_h_p16.hip: the variants that read a P16 tensor
+hipError_t c3h16_launch(int key, const ConvArgs& a, int n_groups, hipStream_t stream);
+hipError_t c3h1_init_kernels();                                 // conv3_h_fast16.hip: one product per MAC (option "fast16"), both input forms
+hipError_t c3h1_launch(int key, const ConvArgs& a, int n_groups, hipStream_t stream);
 
 }  // namespace dcscn

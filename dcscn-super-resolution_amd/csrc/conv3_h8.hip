@@ -3,26 +3,12 @@
 
 namespace dcscn {
 
-template <int NT, int C1>
-static hipError_t c3e_set_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_h8<NT, C1>), hipFuncAttributeMaxDynamicSharedMemorySize, C3EGeom<NT>::LDS_BYTES);
-}
-
-hipError_t c3e16_init_kernels();                                // conv3_h8_p16.hip: P16 tensors in and out
-hipError_t c3e16_launch(int nt, const ConvArgs& a, int wgs, hipStream_t stream);
-hipError_t c3e1_init_kernels();                                 // conv3_h8_fast16.hip: one product per MAC (option "fast16"), float32 or P16 tensors
-hipError_t c3e1_launch(int nt, const ConvArgs& a, int wgs, bool p16, hipStream_t stream);
+using List = C3EVariants<false, 3>;
 
 hipError_t c3e_init_kernels() {
     hipError_t e = c3e16_init_kernels();
     if (e == hipSuccess) e = c3e1_init_kernels();
-    if (e != hipSuccess) return e;
-    e = c3e_set_attr<6, 6>();
-    if (e == hipSuccess) e = c3e_set_attr<6, 5>();
-    if (e == hipSuccess) e = c3e_set_attr<5, 5>();
-    if (e == hipSuccess) e = c3e_set_attr<5, 4>();
-    if (e == hipSuccess) e = c3e_set_attr<4, 4>();
-    return e != hipSuccess ? e : c3e_set_attr<4, 3>();
+    return e != hipSuccess ? e : List::set_attrs();
 }
 
 // conv3_h8 takes the launches conv3_h would run with exactly two channel groups of nt >= 4 tiles (the pair (nt, nt) or (nt, nt - 1)),
@@ -30,12 +16,6 @@ hipError_t c3e_init_kernels() {
 bool c3e_eligible(int nt, const ConvArgs& a, int n_groups) {
     return n_groups == 2 && nt >= 4 && nt <= 6 && a.n_full >= 1 && a.n_full <= 2 && a.ps == 1 && a.res == nullptr && (a.act == ACT_ALPHA || a.act == ACT_NONE) &&
            a.n_chunks >= 3;
-}
-
-template <int NT, int C1>
-static hipError_t c3e_launch_one(const ConvArgs& a, int wgs, hipStream_t stream) {
-    hipLaunchKernelGGL((conv3_h8<NT, C1>), dim3((unsigned)wgs), dim3(512), C3EGeom<NT>::LDS_BYTES, stream, a);
-    return hipGetLastError();
 }
 
 hipError_t c3e_launch(int nt, const ConvArgs& args, int n_groups, int n_cus, hipStream_t stream, bool fast16) {
@@ -48,16 +28,12 @@ hipError_t c3e_launch(int nt, const ConvArgs& args, int n_groups, int n_cus, hip
     const int wgs = (int)(units < n_cus ? units : n_cus);                 // one persistent workgroup per CU
     // P16 in and out (p16.hpp): the variant that stages its image by LDS-DMA; float32 in and out: the r04 kernel; anything mixed is not ours
     const bool out16 = a.out0.p16.base != nullptr && (a.split >= (1 << 29) || a.out1.p16.base != nullptr);
-    if (a.in16.base && out16) return fast16 ? c3e1_launch(nt, a, wgs, true, stream) : c3e16_launch(nt, a, wgs, stream);
-    if (a.in16.base || a.out0.p16.base || a.out1.p16.base) return hipErrorInvalidValue;
-    if (fast16) return c3e1_launch(nt, a, wgs, false, stream);
-    const bool eq = a.n_full == 2;
-    switch (nt) {
-        case 6: return eq ? c3e_launch_one<6, 6>(a, wgs, stream) : c3e_launch_one<6, 5>(a, wgs, stream);
-        case 5: return eq ? c3e_launch_one<5, 5>(a, wgs, stream) : c3e_launch_one<5, 4>(a, wgs, stream);
-        case 4: return eq ? c3e_launch_one<4, 4>(a, wgs, stream) : c3e_launch_one<4, 3>(a, wgs, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const bool p16 = a.in16.base && out16;
+    if (!p16 && (a.in16.base || a.out0.p16.base || a.out1.p16.base)) return hipErrorInvalidValue;
+    const int key = c3e_key(nt, a.n_full == 2 ? nt : nt - 1, p16);
+    if (fast16) return c3e1_launch(key, a, wgs, stream);
+    if (p16) return c3e16_launch(key, a, wgs, stream);
+    return List::launch(key, a, wgs, stream);
 }
 
 }  // namespace dcscn

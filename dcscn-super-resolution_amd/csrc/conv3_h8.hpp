@@ -630,4 +630,31 @@ __global__ __launch_bounds__(512, 2) void conv3_h8(const ConvArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // no LDS-DMA may land after the workgroup has given its LDS back
 }
 
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation; a: eligible and completed by c3e_launch, which also
+// decides P16 (P16 tensors in and out, or float32 in and out) ----
+constexpr int c3e_key(int nt, int c1, bool p16) { return (8 * nt + c1) * 2 + p16; }
+
+template <int NT, int C1, bool P16, int NP>
+struct C3EVariant {
+    static constexpr int KEY = c3e_key(NT, C1, P16);
+    static constexpr auto kernel = &conv3_h8<NT, C1, NT, P16, NP>;
+    static constexpr int THREADS = C3EGeom<NT>::THREADS, LDS = C3EGeom<NT>::LDS_BYTES;
+    static hipError_t set_attr() { return allow_lds(kernel, LDS); }
+    static hipError_t launch(const ConvArgs& a, int wgs, hipStream_t stream) {
+        if (P16 && (long long)a.N * a.H * a.W > kP16MaxPixels) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(THREADS), LDS, stream, a);
+        return hipGetLastError();
+    }
+};
+// the group pairs (nt, nt) and (nt, nt - 1) of one (tensor form, products per MAC)
+template <bool P16, int NP>
+using C3EVariants = Variants<C3EVariant<6, 6, P16, NP>, C3EVariant<6, 5, P16, NP>, C3EVariant<5, 5, P16, NP>, C3EVariant<5, 4, P16, NP>, C3EVariant<4, 4, P16, NP>,
+                             C3EVariant<4, 3, P16, NP>>;
+
+// the translation units behind c3e_launch (key = c3e_key)
+hipError_t c3e16_init_kernels();                                // conv3_h8_p16.hip: P16 tensors in and out
+hipError_t c3e16_launch(int key, const ConvArgs& a, int wgs, hipStream_t stream);
+hipError_t c3e1_init_kernels();                                 // conv3_h8_fast16.hip: one product per MAC (option "fast16"), float32 or P16 tensors
+hipError_t c3e1_launch(int key, const ConvArgs& a, int wgs, hipStream_t stream);
+
 }  // namespace dcscn

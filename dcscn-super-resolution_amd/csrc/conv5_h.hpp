@@ -487,4 +487,47 @@ __global__ __launch_bounds__(256, 2) void fold_border(const ConvArgs a) {
     if (chk != chk && a.redo) { a.redo[0] = 1; a.redo[1 + img] = 1; }
 }
 
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation; arguments checked by c5h_launch / c5h_border_launch ----
+constexpr int c5h_key(int nt, bool in16) { return 2 * nt + in16; }
+
+template <int NT, bool IN16, int NP>
+struct C5HVariant {
+    static constexpr int KEY = c5h_key(NT, IN16);
+    static constexpr auto kernel = &conv5_h<NT, IN16, NP>;
+    static constexpr int THREADS = C5HGeom<NT>::THREADS, LDS = C5HGeom<NT>::LDS_BYTES;
+    static hipError_t set_attr() { return allow_lds(kernel, LDS); }
+    static hipError_t launch(const ConvArgs& a, hipStream_t stream) {
+        const long long tiles = (long long)a.N * a.tiles_y * a.tiles_x;
+        if (tiles > 0x7fffffffLL || (IN16 && (long long)a.N * a.H * a.W > kP16MaxPixels)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(THREADS), LDS, stream, a);
+        return hipGetLastError();
+    }
+};
+template <int NT, int NP>
+using C5HInputs = Variants<C5HVariant<NT, false, NP>, C5HVariant<NT, true, NP>>;
+// nt = ceil(4 ps^2 / 16) of the x2 / x3 / x4 tails, both input forms
+template <int NP>
+using C5HVariants = decltype(C5HInputs<1, NP>{} + C5HInputs<3, NP>{} + C5HInputs<4, NP>{});
+
+template <bool IN16, int NP>
+struct FoldBorderVariant {            // key = the input form
+    static constexpr int KEY = IN16;
+    static constexpr auto kernel = &fold_border<IN16, NP>;
+    static constexpr int THREADS = 256, LDS = 4 * kFbWinBytes;      // four jobs (waves) per workgroup, a window each
+    static hipError_t set_attr() { return allow_lds(kernel, LDS); }
+    static hipError_t launch(const ConvArgs& a, hipStream_t stream) {
+        const long long grid = (fold_border_jobs(a.N, a.H, a.W).total + 3) / 4;
+        if (grid > 0x7fffffffLL || (IN16 && (long long)a.N * a.H * a.W > kP16MaxPixels)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(THREADS), LDS, stream, a);
+        return hipGetLastError();
+    }
+};
+template <int NP>
+using FoldBorderVariants = Variants<FoldBorderVariant<false, NP>, FoldBorderVariant<true, NP>>;
+
+// the translation unit behind c5h_launch / c5h_border_launch (keys as above): conv5_h_fast16.hip, one product per MAC (option "fast16")
+hipError_t c5h1_init_kernels();
+hipError_t c5h1_launch(int key, const ConvArgs& a, hipStream_t stream);
+hipError_t c5h1_border_launch(int key, const ConvArgs& a, hipStream_t stream);
+
 }  // namespace dcscn

@@ -3,50 +3,13 @@
 
 namespace dcscn {
 
-constexpr int kNinMaxTable = 16 * 1024;          // LDS bytes for the multi-source quad table: 1024 quads = 4096 input channels
+using List = decltype(NinVariants<false>{} + NinVariants<true>{});
 
-template <int NT>
-static hipError_t nin_set_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_nin<NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, NinGeom<NT>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_nin<NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               NinGeom<NT>::LDS_BYTES + kNinMaxTable);
-}
-
-hipError_t nin_init_kernels() {
-    hipError_t e = nin_set_attr<1>();
-    if (e == hipSuccess) e = nin_set_attr<2>();
-    if (e == hipSuccess) e = nin_set_attr<3>();
-    if (e == hipSuccess) e = nin_set_attr<4>();
-    if (e == hipSuccess) e = nin_set_attr<5>();
-    return e != hipSuccess ? e : nin_set_attr<6>();
-}
-
-template <int NT>
-static hipError_t nin_launch_one(const ConvArgs& a, int n_groups, hipStream_t stream) {
-    const long long npix = (long long)a.N * a.H * a.W;
-    const dim3 grid((unsigned)((npix + NinGeom<NT>::PIX - 1) / NinGeom<NT>::PIX), (unsigned)n_groups);
-    if (a.srctab) {
-        const size_t table = (size_t)a.n_chunks * 64;
-        if (table > (size_t)kNinMaxTable) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((conv_nin<NT, true>), grid, dim3(256), NinGeom<NT>::LDS_BYTES + table, stream, a);
-    } else {
-        hipLaunchKernelGGL((conv_nin<NT, false>), grid, dim3(256), NinGeom<NT>::LDS_BYTES, stream, a);
-    }
-    return hipGetLastError();
-}
+hipError_t nin_init_kernels() { return List::set_attrs(); }
 
 hipError_t nin_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream) {
     if (a.n_full < 1 || a.n_full > n_groups || (nt == 1 && a.n_full != n_groups)) return hipErrorInvalidValue;
-    switch (nt) {
-        case 1: return nin_launch_one<1>(a, n_groups, stream);
-        case 2: return nin_launch_one<2>(a, n_groups, stream);
-        case 3: return nin_launch_one<3>(a, n_groups, stream);
-        case 4: return nin_launch_one<4>(a, n_groups, stream);
-        case 5: return nin_launch_one<5>(a, n_groups, stream);
-        case 6: return nin_launch_one<6>(a, n_groups, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return List::launch(nin_key(nt, a.srctab != nullptr), a, n_groups, stream);
 }
 
 }  // namespace dcscn

@@ -244,4 +244,27 @@ __global__ __launch_bounds__(256, WPS) void conv_nin(const ConvArgs a) {
     else if constexpr (NT >= 2) conv_nin_body<NT, NT - 1, MULTI>(a, smem, pix0, ntile);
 }
 
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation; arguments checked by nin_launch ----
+constexpr int kNinMaxTable = 16 * 1024;          // LDS bytes for the source table of conv_nin and conv_nin_h: 1024 quads = 4096 input channels
+constexpr int nin_key(int nt, bool multi) { return 2 * nt + multi; }
+
+template <int NT, bool MULTI>
+struct NinVariant {
+    static constexpr int KEY = nin_key(NT, MULTI);
+    static constexpr auto kernel = &conv_nin<NT, MULTI>;
+    static constexpr int THREADS = NinGeom<NT>::THREADS, LDS = NinGeom<NT>::LDS_BYTES, MAX_LDS = LDS + (MULTI ? kNinMaxTable : 0);
+    static hipError_t set_attr() { return allow_lds(kernel, MAX_LDS); }
+    static hipError_t launch(const ConvArgs& a, int n_groups, hipStream_t stream) {
+        const long long npix = (long long)a.N * a.H * a.W;
+        const size_t table = MULTI ? (size_t)a.n_chunks * 64 : 0;       // 4 quads of 16 bytes per 16-channel chunk
+        if (table > (size_t)kNinMaxTable) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)((npix + NinGeom<NT>::PIX - 1) / NinGeom<NT>::PIX), (unsigned)n_groups);
+        hipLaunchKernelGGL(kernel, grid, dim3(THREADS), LDS + table, stream, a);
+        return hipGetLastError();
+    }
+};
+template <bool MULTI>
+using NinVariants = Variants<NinVariant<1, MULTI>, NinVariant<2, MULTI>, NinVariant<3, MULTI>, NinVariant<4, MULTI>, NinVariant<5, MULTI>, NinVariant<6, MULTI>>;
+static_assert(kNinMaxNT == 6, "NinVariants lists NT 1 .. kNinMaxNT");
+
 }  // namespace dcscn

@@ -275,4 +275,47 @@ __global__ __launch_bounds__(64 * WAVES, (WPS * WAVES / 4) * 128 / (16 * MT * WA
     else if constexpr (NT >= 2) conv_nin_h_body<NT, NT - 1, SRC, S, WAVES, MT, NP>(a, smem, pix0, ntile);
 }
 
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation; arguments checked by nin_h_launch ----
+constexpr int kNinHStages = 3;                   // input stages: chunk c + 3 is fetched while chunk c computes (3.02 vs 3.08 ms with 2)
+// the wide workgroup: 8 waves x two 16-pixel tiles = 256 pixels, ONE workgroup per CU, half the filter traffic per pixel.  Same products
+// in the same order per pixel: bit-identical to the 128-pixel workgroups.  Measured same-box in r05 (profiles/r05_ninh_ablation.txt):
+// -3 % on the 1301-channel GEMM of the L12 nets, +7 ... +9 % on 540 / 131 channels -- so only the wide K axes take it, with P16
+// sources and six output tiles
+constexpr int kNinH8Waves = 8, kNinH8Tiles = 2;
+constexpr int kNinH8MinChunks = 32;              // K >= 1024 channels (-3 % at 1301; slower at 540)
+constexpr int nin_h_key(int nt, int src, bool wide) { return (3 * nt + src) * 2 + wide; }
+
+template <int NT, int SRC, int WAVES, int MT, int NP>
+struct NinHVariant {
+    using G = NinHGeom<NT, kNinHStages, WAVES, MT>;
+    static constexpr int KEY = nin_h_key(NT, SRC, WAVES == kNinH8Waves);
+    static constexpr auto kernel = &conv_nin_h<NT, SRC, kNinHStages, 2, WAVES, MT, NP>;
+    // source table bytes per 32-channel chunk: P16 sources one 16-byte entry per channel OCTET (4), multi-source 8 quads of 16 bytes
+    static constexpr int CHUNK_TABLE = SRC == 2 ? 64 : SRC == 1 ? 128 : 0;
+    static constexpr int THREADS = G::THREADS, LDS = G::LDS_BYTES, MAX_LDS = LDS + (SRC ? kNinMaxTable : 0);
+    static hipError_t set_attr() { return allow_lds(kernel, MAX_LDS); }
+    static hipError_t launch(const ConvArgs& a, int n_groups, hipStream_t stream) {
+        const long long npix = (long long)a.N * a.H * a.W;
+        const size_t table = SRC ? (size_t)a.n_chunks * CHUNK_TABLE : 0;
+        if (table > (size_t)kNinMaxTable || (SRC == 2 && (!a.in16.base || !a.srctab || npix > kP16MaxPixels))) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)((npix + G::PIX - 1) / G::PIX), (unsigned)n_groups);
+        hipLaunchKernelGGL(kernel, grid, dim3(THREADS), LDS + table, stream, a);
+        return hipGetLastError();
+    }
+};
+// the 128-pixel workgroups (4 waves x 2 tiles): every NT of the three source forms; the wide workgroup: six tiles, P16 sources
+template <int SRC, int NP>
+using NinHSource = Variants<NinHVariant<1, SRC, 4, 2, NP>, NinHVariant<2, SRC, 4, 2, NP>, NinHVariant<3, SRC, 4, 2, NP>, NinHVariant<4, SRC, 4, 2, NP>,
+                            NinHVariant<5, SRC, 4, 2, NP>, NinHVariant<6, SRC, 4, 2, NP>>;
+template <int NP>
+using NinHNarrow = decltype(NinHSource<0, NP>{} + NinHSource<1, NP>{} + NinHSource<2, NP>{});
+template <int NP>
+using NinHWide = Variants<NinHVariant<6, 2, kNinH8Waves, kNinH8Tiles, NP>>;
+
+// the translation units behind nin_h_launch (key = nin_h_key)
+hipError_t nin_h8_init_kernels();                                // conv_nin_h_w8.hip: the wide workgroup
+hipError_t nin_h8_launch(int key, const ConvArgs& a, int n_groups, hipStream_t stream);
+hipError_t nin_h1_init_kernels();                                // conv_nin_h_fast16.hip: one product per MAC (option "fast16"), both workgroup sizes
+hipError_t nin_h1_launch(int key, const ConvArgs& a, int n_groups, hipStream_t stream);
+
 }  // namespace dcscn

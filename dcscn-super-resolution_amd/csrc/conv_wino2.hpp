@@ -26,6 +26,7 @@
 // is the explicit one.
 #pragma once
 #include "conv_igemm.hpp"
+#include "variant_list.hpp"
 
 namespace dcscn {
 
@@ -411,5 +412,27 @@ __global__ __launch_bounds__(256, 1) void conv_wino2_redo(const ConvArgs a) {
         }
     }
 }
+
+// ---- host side (variant_list.hpp): the launch parameters of one instantiation and its _redo twin; arguments checked by wino_launch ----
+template <int NT>
+struct WinoVariant {
+    static constexpr int KEY = NT;
+    static constexpr auto kernel = &conv_wino2<NT>, kernel_redo = &conv_wino2_redo<NT>;
+    static constexpr int THREADS = Wino2Geom<NT>::THREADS, LDS = Wino2Geom<NT>::LDS_BYTES;
+    static hipError_t set_attr() {
+        const hipError_t e = allow_lds(kernel, LDS);
+        return e != hipSuccess ? e : allow_lds(kernel_redo, LDS);
+    }
+    static hipError_t launch(ConvArgs a, int n_groups, hipStream_t stream) {
+        const long long ids = xcd_grid_ids(a, n_groups), tiles = (long long)a.N * a.tiles_y * a.tiles_x;
+        if (a.redo_check)                                          // behind conv3_h: 64 tile flags per workgroup (conv_wino2_redo)
+            hipLaunchKernelGGL(kernel_redo, dim3((unsigned)((tiles + 63) / 64)), dim3(THREADS), LDS, stream, a);
+        else
+            hipLaunchKernelGGL(kernel, dim3((unsigned)ids), dim3(THREADS), LDS, stream, a);
+        return hipGetLastError();
+    }
+};
+using WinoVariants = Variants<WinoVariant<1>, WinoVariant<2>, WinoVariant<3>>;
+static_assert(kWinoMaxNT == 3, "WinoVariants lists NT 1 .. kWinoMaxNT");
 
 }  // namespace dcscn

@@ -145,6 +145,16 @@ inline int c3h_tail_octs(int cin_phys) {
     return n_chunks < 2 || tail > 24 ? 0 : (tail + 7) / 8;
 }
 inline int c3h_tail_steps(int octs) { return (9 * octs + 3) / 4; }
+// The 1-D grid of conv_wino2 / conv3_h, which decode (pixel tile, group) from it XCD-aware: the groups of one pixel tile get ids that are
+// congruent mod 8 and close together, up to three groups at a time (r01, measured: span 1 / 2 / 3 / 4 / 8 -> 49.19 / 48.63 / 47.95 /
+// 48.39 / 48.30 ms per step), the rest in further phases.  Writes n_groups and group_span into `a`, returns the workgroup count.
+inline long long xcd_grid_ids(ConvArgs& a, int n_groups) {
+    a.n_groups = n_groups;
+    a.group_span = n_groups < 3 ? n_groups : 3;
+    const long long tiles = (long long)a.N * a.tiles_y * a.tiles_x;
+    const int phases = (n_groups + a.group_span - 1) / a.group_span;
+    return ((tiles + 7) / 8) * 8 * a.group_span * phases;
+}
 hipError_t c3h_init_kernels();
 hipError_t c3h_launch(int nt, const ConvArgs& a, int n_groups, hipStream_t stream, bool fast16 = false);
 // conv3_h8 (conv3_h8.hpp): conv3_h's launches with exactly two channel groups as ONE persistent 8-wave workgroup per CU -- the pixel

@@ -61,13 +61,7 @@ static std::vector<float> pack_wino2(const std::vector<float>& w, int cin, int c
     return p;
 }
 
-static dim3 tiles_grid(ConvArgs& a, int n_groups) {
-    a.n_groups = n_groups;
-    a.group_span = n_groups < 3 ? n_groups : 3;
-    const long long tiles = (long long)a.N * a.tiles_y * a.tiles_x;
-    const int phases = (n_groups + a.group_span - 1) / a.group_span;
-    return dim3((unsigned)(((tiles + 7) / 8) * 8 * a.group_span * phases));
-}
+static dim3 tiles_grid(ConvArgs& a, int n_groups) { return dim3((unsigned)xcd_grid_ids(a, n_groups)); }
 
 struct R3 { double e32, e16, maxv; float ms32, ms16, mshp, msh8; int bad; };
 static int g_h8_wgs = 256;        // persistent workgroups of conv3_h8 (env C3E_WGS)
