@@ -356,6 +356,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->fast16 = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "train_split16")) {            // any time: the next gradient computation re-carves the training arena (train.hip: carve)
+        h->train_split16 = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
         h->p16 = value != 0;
         return DCSCN_OK;

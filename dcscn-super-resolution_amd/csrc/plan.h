@@ -259,6 +259,7 @@ struct dcscn_ctx {
     std::vector<int> ev_op;                  // launch index of each recorded pair (ops.size() = the float32 plan behind a pass)
     int ev_forwards = 0;                     // forwards recorded since the last dcscn_get_profile
     std::vector<void*> pack_allocs;          // device images finalize_op made (freed and rebuilt when training changed the variables)
+    bool train_split16 = false;              // option "train_split16": eligible forward / data-gradient convs of the training plan on tconv_gemm_h (train_h.hpp)
     dcscn_impl::TrainState* train = nullptr;      // train.hip: the training plan, variables and slots (dcscn_train_begin)
     dcscn_impl::TrainBatches* batches = nullptr;  // train_data.hip: device-resident training images and the batch planes
 };

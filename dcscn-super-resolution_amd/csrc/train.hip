@@ -12,6 +12,7 @@
 // Variables, their gradients and the optimizer slots live in flat f32 buffers in the checkpoint (HWIO) layout, in the order of
 // the graph's variable list (dcscn_tensor_info), so the update is one elementwise launch.
 #include "plan.h"
+#include "train_h.hpp"
 
 #pragma clang fp contract(off)
 
@@ -478,6 +479,10 @@ struct TLayer {
     int ps = 0;                    // > 0: Up-PS conv followed by depth_to_space with this factor
     int w_t = -1, b_t = -1, a_t = -1;
     float* z = nullptr;            // pre-activation, dense [P res^2, cout]
+    // option "train_split16" (train_h.hpp), in the current carve: h16 = the layer's forward and data-gradient convs run on tconv_gemm_h
+    bool h16 = false;
+    void *w16 = nullptr, *wd16 = nullptr;   // tpack_h images: forward, data gradient (null for a layer on the network input)
+    int* e = nullptr;                       // exponents of the scales: [0] filter, [1] input slice, [2] dz
 };
 
 // the variables the l2 term sums over: the filters, not biases or prelu slopes
@@ -496,6 +501,8 @@ struct TrainState {
     // arena for the current batch shape
     void* arena = nullptr; size_t arena_bytes = 0;
     int n = 0, H = 0, W = 0;
+    bool h16 = false;              // the carve holds the filter images and exponents of option "train_split16"
+    unsigned* absmax = nullptr;    // kAbsMaxBlocks partial maxima (launch_texp)
     float *dz = nullptr, *at = nullptr, *part = nullptr, *col = nullptr, *zlast = nullptr, *dzlast = nullptr, *clip = nullptr;
     float *io_x = nullptr, *io_x2 = nullptr, *io_y = nullptr;
     double *dpart = nullptr, *d_stats = nullptr;
@@ -600,7 +607,8 @@ static int col_splits(int64_t P, int64_t* chunk) {
 }
 
 static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
-    if (t->arena && t->n == n && t->H == H && t->W == W) return DCSCN_OK;
+    const bool h16 = h->train_split16;
+    if (t->arena && t->n == n && t->H == H && t->W == W && t->h16 == h16) return DCSCN_OK;
     const int64_t P = (int64_t)n * H * W;
     size_t bytes = 0;
     auto take = [&](size_t floats) { size_t o = bytes; bytes += (floats * 4 + 255) / 256 * 256; return o; };
@@ -627,6 +635,19 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
     const size_t o_dz = take(dz_max), o_at = take(dz_max), o_part = take(part_max), o_col = take(col_max);
     const size_t o_x = take((size_t)P), o_x2 = take(hr), o_y = take(hr), o_clip = take(4);
     const size_t o_dpart = take(2 * (2 * kLossBlocks + (size_t)t->w2_blocks + kNormBlocks) + 16);
+    // option "train_split16": both filter images of every eligible layer, three exponents per layer, the partial maxima
+    std::vector<size_t> ow(t->layers.size(), 0), owd(t->layers.size(), 0);
+    size_t o_exp = 0, o_absmax = 0;
+    if (h16) {
+        for (size_t l = 0; l < t->layers.size(); ++l) {
+            const TLayer& L = t->layers[l];
+            if (!tconv_h_eligible(L.cin, L.cout)) continue;
+            ow[l] = take(tpack_h_bytes(L.ks * L.ks, L.cin, L.cout) / 4);
+            if (L.in_buf >= 0) owd[l] = take(tpack_h_bytes(L.ks * L.ks, L.cout, L.cin) / 4);
+        }
+        o_exp = take(3 * t->layers.size());
+        o_absmax = take(kAbsMaxBlocks);
+    }
     if ((int64_t)bytes > h->workspace_budget)
         return fail(h, DCSCN_ERR_NOMEM, "training batch %d x %d x %d needs %zu bytes of workspace, over the budget of %lld (training does not tile)",
                     n, H, W, bytes, (long long)h->workspace_budget);
@@ -636,7 +657,16 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
     t->arena_bytes = bytes;
     char* base = static_cast<char*>(t->arena);
     for (size_t b = 0; b < t->bufs.size(); ++b) { t->bufs[b].h = (float*)(base + oh[b]); t->bufs[b].g = (float*)(base + og[b]); }
-    for (size_t l = 0; l < t->layers.size(); ++l) t->layers[l].z = (float*)(base + oz[l]);
+    for (size_t l = 0; l < t->layers.size(); ++l) {
+        TLayer& L = t->layers[l];
+        L.z = (float*)(base + oz[l]);
+        L.h16 = h16 && tconv_h_eligible(L.cin, L.cout);
+        L.w16 = L.h16 ? base + ow[l] : nullptr;
+        L.wd16 = L.h16 && L.in_buf >= 0 ? base + owd[l] : nullptr;
+        L.e = L.h16 ? (int*)(base + o_exp) + 3 * l : nullptr;
+    }
+    t->h16 = h16;
+    t->absmax = h16 ? (unsigned*)(base + o_absmax) : nullptr;
     t->dz = (float*)(base + o_dz); t->at = (float*)(base + o_at); t->part = (float*)(base + o_part); t->col = (float*)(base + o_col);
     t->io_x = (float*)(base + o_x); t->io_x2 = (float*)(base + o_x2); t->io_y = (float*)(base + o_y); t->clip = (float*)(base + o_clip);
     t->dpart = (double*)(base + o_dpart);
@@ -663,6 +693,15 @@ static int launch_conv(dcscn_ctx* h, hipStream_t st, const float* in, int in_str
     return DCSCN_OK;
 }
 
+// the same conv on tconv_gemm_h (option "train_split16"): the exponent of the input's scale first, then the launch that reads it
+static int launch_conv_h(dcscn_ctx* h, TrainState* t, hipStream_t st, const float* in, int in_stride, int cin, int n, int H, int W, int ks, const void* w16,
+                         const int* e_w, int* e_in, int cout, const float* bias, float* out, int out_stride, int accumulate) {
+    KTRY(h, launch_texp(in, in_stride, cin, (int64_t)n * H * W, t->absmax, e_in, st));
+    TConvHArgs a{in, in_stride, cin, n, H, W, ks, w16, cout, bias, out, out_stride, e_in, e_w};
+    KTRY(h, launch_tconv_gemm_h(a, accumulate, st));
+    return DCSCN_OK;
+}
+
 // forward + backward of one step (gradients into d_g, stats into d_stats); no host synchronisation
 static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const float* x2, const float* yt, uint64_t key, hipStream_t st,
                          int64_t first_index = 0) {
@@ -683,6 +722,11 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
     // dgrad filters of the current weights
     for (const TLayer& L : t->layers) {
         const int64_t cnt = (int64_t)L.ks * L.ks * L.cin * L.cout;
+        if (L.h16) {   // the scaled f16 images of both directions instead
+            KTRY(h, launch_texp(t->d_w + t->off[L.w_t], 1, 1, cnt, t->absmax, L.e, st));
+            KTRY(h, launch_tpack_h(t->d_w + t->off[L.w_t], L.ks * L.ks, L.cin, L.cout, L.e, L.w16, L.wd16, st));
+            continue;
+        }
         KTRY(h, hipLaunchKernelGGL(tpack_dgrad, dim3(grid1(cnt)), dim3(256), 0, st, t->d_w + t->off[L.w_t], L.ks * L.ks, L.cin, L.cout, t->d_wd + t->off[L.w_t]));
     }
     // ---- forward ----
@@ -691,8 +735,9 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         const int64_t px = P * r * r;
         float* gdummy;
         const float* in = in_ptr(L, &gdummy);
-        int rc = launch_conv(h, st, in, in_stride(L), L.cin, n, H * r, W * r, L.ks, t->d_w + t->off[L.w_t], L.cout,
-                             L.b_t >= 0 ? t->d_w + t->off[L.b_t] : nullptr, L.z, L.cout, 0);
+        const float* bias = L.b_t >= 0 ? t->d_w + t->off[L.b_t] : nullptr;
+        int rc = L.h16 ? launch_conv_h(h, t, st, in, in_stride(L), L.cin, n, H * r, W * r, L.ks, L.w16, L.e, L.e + 1, L.cout, bias, L.z, L.cout, 0)
+                       : launch_conv(h, st, in, in_stride(L), L.cin, n, H * r, W * r, L.ks, t->d_w + t->off[L.w_t], L.cout, bias, L.z, L.cout, 0);
         if (rc) return rc;
         if (L.dropout) {
             const TBuf& ob = t->bufs[L.out_buf];
@@ -751,7 +796,8 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         }
         // data gradient, accumulated into the input's gradient (none for the network input)
         if (gin) {
-            int rc = launch_conv(h, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, t->d_wd + t->off[L.w_t], L.cin, nullptr, gin, in_stride(L), 1);
+            int rc = L.h16 ? launch_conv_h(h, t, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, L.wd16, L.e, L.e + 2, L.cin, nullptr, gin, in_stride(L), 1)
+                           : launch_conv(h, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, t->d_wd + t->off[L.w_t], L.cin, nullptr, gin, in_stride(L), 1);
             if (rc) return rc;
         }
     }

@@ -92,6 +92,8 @@ class SuperResolution:
         self.device_metrics = bool(getattr(flags, "device_metrics", False))
         # extension: forwards take one f16 product per MAC (engine option "fast16"; set on every engine this model creates)
         self.fast16 = bool(getattr(flags, "fast16", False))
+        # extension: training takes the wide layers' forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16")
+        self.train_split16 = bool(getattr(flags, "train_split16", False))
 
         # training parameters (DCSCN.py:50-93)
         fget = lambda k, d: getattr(flags, k, d)
@@ -391,6 +393,8 @@ class SuperResolution:
             if self._data_parallel():
                 self.step = self.train_group.broadcast_object(self.step)   # the dropout key counts steps: rank 0's, when resuming
             eng.train_begin(self._train_flags)
+            if self.train_split16:
+                eng.set_option("train_split16", 1)
             self._train_engine = eng
             self._device_images = {}
             if self._pending_slots:

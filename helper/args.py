@@ -90,6 +90,8 @@ _TABLE = [
     (_B, "device_metrics", False, "compute the PSNR and SSIM of evaluated images on the device"),
     # ---- extension (not a reference flag): inference with ONE f16 product per multiply-accumulate (engine option "fast16", include/dcscn.h)
     (_B, "fast16", False, "inference at f16 operand accuracy: one matrix product per MAC instead of three (training is unaffected)"),
+    # ---- extension (not a reference flag): training's wide forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16", include/dcscn.h)
+    (_B, "train_split16", False, "training at f32 accuracy with the forward and data-gradient convs of layers with min(cin, cout) >= 16 as three scaled f16 products"),
     # ---- frozen graphs (args.py:97-98): weights from the Const nodes of a frozen GraphDef (dcscn-super-resolution_amd/frozen.py)
     (_B, "frozenInference", False, "Flag for whether the model to evaluate is frozen."),
     (_S, "frozen_graph_path", "./model_to_freeze/frozen_model_optimized.pb", "the path to a frozen model if performing inference from it"),

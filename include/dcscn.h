@@ -233,6 +233,18 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * 1.5e-5 and 1/200 of an 8-bit step.  Measured on an MI355X: 2.3e-3 / 6.2e-4 (L12 x2), 3.1e-3 / 8.0e-4 (L12 x4), 3.5e-3 / 8.7e-4 (L8 x2);
  * with the shipped c-DCSCN x2 weights, layer by layer, 1.3e-2 / 1.5e-3.  A 1024-patch pass of L12 x2 takes 0.667 of its time (DESIGN.md
  * 3.13).  Not f32 accuracy, not bf16 / fp8, not for training.
+ * "train_split16" (default 0; any time, also before dcscn_train_begin; takes effect from the next gradient computation, which re-carves
+ * the training workspace): an opt-in training mode at the f32 path's accuracy.  With 1, every layer of the training plan with
+ * min(cin, cout) >= 16 -- a rule of the layer's shape alone, the same for both directions -- takes its forward conv and its data-gradient
+ * conv on the f16 matrix pipe (tconv_gemm_h) as three f16 products wh * xh + wh * xl + wl * xh per multiply-accumulate, accumulated in
+ * f32; narrower layers (CNN1, the last R-CNN), the weight gradients, activators, dropout, loss, clipping, the optimizers and the record
+ * calls are the f32 path's, and the weight gradient consumes the dz the split16 data gradient produced.  Unlike the inference "split16",
+ * EVERY operand is scaled before it is split: the layer's input slice, dz and the filter are multiplied by 2^e, e chosen on the device
+ * (a max reduction: no atomics, no host synchronisation) so that the tensor's largest magnitude lies in [2^13, 2^14); e = 0 for an
+ * all-zero tensor and |e| <= 126.  Gradients of 1e-6 and below therefore keep their lo pieces normal, no operand can leave the f16 range,
+ * and the mode has no redo flags and no float32 fallback; the epilogue undoes both scales with ldexp (exact).  A non-finite value in an
+ * operand gives non-finite results, as on the f32 path.  Same parity bars as the default mode (1e-4 * max|g| per gradient tensor),
+ * deterministic, but not the default mode's bits.  0 allocates and launches exactly what a handle that never set the option does.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The
@@ -356,7 +368,8 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  * Training (DCSCN.py:334-425, 727-769): f32, non-separable pixel-shuffler nets only; one device per handle, several handles
  * (one per rank) train data-parallel through the record calls below.
  *
- * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no split16, no Winograd), with
+ * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no Winograd, none of the inference split16
+ * kernels; option "train_split16" moves the wide layers' forward and data-gradient convs to the f16 matrix pipe at f32 accuracy), with
  * dropout after the activator of every conv that has one (CNN1..L, A1, B1, B2, C, the non-final R-CNN layers; not the Up-PS
  * convs, not the last R-CNN): out = h / keep where the mask is 1, else 0.
  * Loss: diff = (R-CNN_last + x2) - y_true over the whole HR patch; mse = mean(diff^2); image_loss = mse, or mean(|diff|) with

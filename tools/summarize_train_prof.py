@@ -4,7 +4,9 @@
 
 Phases: forward (tconv_gemm<0>, tact_fwd, td2s), dgrad (tconv_gemm<1>, tpack_dgrad), wgrad (tconv_wgrad, treduce_wgrad,
 tcol_*, tact_bwd), loss (tloss, tsumsq, tstats), optimizer (topt, tpowers).  td2s runs in both directions and is counted
-with the forward; tact_bwd (the activator and dropout backward) is counted with the weight gradient it feeds.
+with the forward; tact_bwd (the activator and dropout backward) is counted with the weight gradient it feeds.  With option
+"train_split16" the eligible layers' convs are tconv_gemm_h<0> (forward) and tconv_gemm_h<1> (dgrad); what the option adds beside
+them -- tabsmax_part, texp_final, tpack_h -- is the phase "scale_pack".  "conv_kernels" lists the conv launches by kernel.
 """
 import csv
 import glob
@@ -12,7 +14,9 @@ import json
 import os
 import sys
 
-PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tpack_dgrad")), ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tact_fwd", "td2s")),
+PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tconv_gemm_hILi1E", "tconv_gemm_h<1>", "tpack_dgrad")),
+          ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tconv_gemm_hILi0E", "tconv_gemm_h<0>", "tact_fwd", "td2s")),
+          ("scale_pack", ("tabsmax_part", "texp_final", "tpack_h")),
           ("wgrad", ("tconv_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
           ("loss", ("tloss", "tsumsq", "tstats")), ("optimizer", ("topt", "tpowers"))]
 
@@ -24,10 +28,13 @@ def main():
         sys.exit("no *kernel_stats.csv under %s" % root)
     ms = {p: 0.0 for p, _ in PHASES}
     other = 0.0
+    convs = {}
     for f in files:
         with open(f) as fh:
             for row in csv.DictReader(fh):
                 name, total_ns = row["Name"], float(row["TotalDurationNs"])
+                if "tconv_" in name:
+                    convs[name] = round(convs.get(name, 0.0) + total_ns / 1e6 / steps, 4)
                 for phase, keys in PHASES:
                     if any(k in name for k in keys):
                         ms[phase] += total_ns / 1e6
@@ -37,7 +44,7 @@ def main():
     per_step = {p: round(v / steps, 4) for p, v in ms.items()}
     per_step["not_training"] = round(other / steps, 4)
     per_step["kernel_sum"] = round(sum(ms.values()) / steps, 4)
-    print(json.dumps({"ms_per_step_by_phase": per_step, "steps": steps, "files": [os.path.relpath(f, root) for f in files]}))
+    print(json.dumps({"ms_per_step_by_phase": per_step, "conv_kernels": convs, "steps": steps, "files": [os.path.relpath(f, root) for f in files]}))
 
 
 if __name__ == "__main__":

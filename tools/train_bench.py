@@ -14,6 +14,13 @@ one process, each timed on the host clock up to the step's stats read-back; one 
 dcscn_train_step_device time of the same batch shape for scale.  --device-only runs only the device leg (profiler runs).
 
     python tools/train_bench.py --loop
+
+--split16 times option "train_split16" = 0 and 1 (include/dcscn.h) on two handles of one process, alternating step by step, for L12 x2
+and c-DCSCN x2 at 20 x 48^2: one JSON line per net with both medians and their ratio.  --train-split16 sets the option on the
+plain run's handle (profiler runs of the option-on step).  --library PATH times another build of the library, e.g. the parent
+commit's, in a process of its own.
+
+    python tools/train_bench.py --split16
 """
 import argparse
 import json
@@ -71,11 +78,46 @@ def batch(cfg, n, h, w):
     return x, x2, y
 
 
-def bench_hip(cfg, n, h, w, steps, warmup):
+def bench_split16(name, n, size, steps, warmup):
+    """train_split16 = 0 and 1 on two handles with the same weights and batch, alternating step by step on one stream."""
+    from dcscn_amd import engine
+    cfg = O.make_config(**CONFIGS[name])
+    engs = []
+    for on in (0, 1):
+        eng = engine.Engine(cfg, device=0)
+        eng.load_weights(O.synthetic_weights(cfg, seed=0))
+        eng.set_option("train_split16", on)
+        eng.train_begin(flags())
+        engs.append(eng)
+    x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, size, size))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    times = ([], [])
+    for i in range(warmup + steps):
+        for on, eng in enumerate(engs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, size, size, 1e-4, i, stream=sp, want_stats=False)
+            b.record(stream)
+            b.synchronize()
+            if i >= warmup:
+                times[on].append(a.elapsed_time(b))
+    for eng in engs:
+        eng.close()
+    off, on = float(np.median(times[0])), float(np.median(times[1]))
+    return dict(split16_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, train_split16_0_ms=round(off, 4),
+                train_split16_1_ms=round(on, 4), ratio_1_over_0=round(on / off, 4),
+                min_ms=[round(float(np.min(times[0])), 4), round(float(np.min(times[1])), 4)])
+
+
+def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False):
     from dcscn_amd import engine
     eng = engine.Engine(cfg, device=0)
     eng.load_weights(O.synthetic_weights(cfg, seed=0))
     eng.train_begin(flags())
+    if train_split16:
+        eng.set_option("train_split16", 1)
     x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, h, w))
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()          # a real stream: the events below are recorded where the steps run
@@ -206,7 +248,17 @@ def main():
     ap.add_argument("--torch-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--loop", action="store_true", help="time build_input_batch() + train_batch() with host and device batches")
     ap.add_argument("--device-only", action="store_true", help="--loop: the device-batch leg only (profiler runs)")
+    ap.add_argument("--split16", action="store_true", help="time train_split16 = 0 and 1 alternating in one process (L12 x2, c-DCSCN x2)")
+    ap.add_argument("--train-split16", action="store_true", help="set option train_split16 on the timed handle")
+    ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
+    if a.library:
+        from dcscn_amd import build
+        build.LIB_PATH = os.path.abspath(a.library)
+    if a.split16:
+        for name in ("L12_x2", "L7_x2"):
+            print(json.dumps(bench_split16(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
+        return
     if a.loop:
         for name, n, size in LOOP_CASES:
             print(json.dumps(bench_loop(name, n, size, a.steps, a.warmup, a.device_only)), flush=True)
@@ -215,7 +267,7 @@ def main():
     if a.torch_only:
         print(json.dumps({"torch_ms_per_step": bench_torch(cfg, a.batch, a.size, a.size, a.steps, a.warmup)}))
         return
-    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup)
+    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup, a.train_split16)
     flops = step_flops(cfg, a.batch, a.size, a.size)
     out = dict(config=a.config, batch=a.batch, lr_size=a.size, steps=a.steps, warmup=a.warmup, ms_per_step=round(med, 4),
                ms_per_step_min=round(best, 4), conv_gflop_per_step=round(flops / 1e9, 3),
