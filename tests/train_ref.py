@@ -47,8 +47,10 @@ def _act(z, kind, alpha):
     raise NameError(kind)
 
 
-def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64):
-    """y_ of the training graph (torch, NCHW) from ``leaves`` {name: tensor}; x, x2 numpy NHWC."""
+def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64, taps=None):
+    """y_ of the training graph (torch, NCHW) from ``leaves`` {name: tensor}; x, x2 numpy NHWC.  ``taps`` {conv variable prefix: anything}
+    asks for those layers' tensors: the entry becomes (pre-activation, output after activator and dropout), torch NCHW, the first
+    with its gradient retained."""
     t = {"x": torch.from_numpy(np.asarray(x, np.float64)).to(dtype).permute(0, 3, 1, 2),
          "x2": torch.from_numpy(np.asarray(x2, np.float64)).to(dtype).permute(0, 3, 1, 2)}
     layer = 0
@@ -60,6 +62,9 @@ def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64):
             h = F.conv2d(t[op["src"]], w, padding=k // 2)
             if op["bias"]:
                 h = h + leaves[v + "/conv_B"].view(1, -1, 1, 1)
+            z = h
+            if taps is not None and v in taps and z.requires_grad:
+                z.retain_grad()
             if op["act"]:
                 alpha = leaves.get(v + "/prelu/" + op["name"] + "_prelu")
                 h = _act(h, op["act"], alpha)
@@ -68,6 +73,8 @@ def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64):
                     m = dropout_mask(key, layer, (n, hh, ww, c), keep)
                     h = (h / keep) * torch.from_numpy(m.astype(np.float64)).to(dtype).permute(0, 3, 1, 2)
             t[op["dst"]] = h
+            if taps is not None and v in taps:
+                taps[v] = (z, h)
             layer += 1
         elif kind == "concat":
             t[op["dst"]] = torch.cat([t[s] for s in op["srcs"]], dim=1)
@@ -87,11 +94,13 @@ def _tf_to_torch_d2s(h, b):
     return h.view(n, b * b, c, hh, ww).transpose(1, 2).reshape(n, cc, hh, ww)
 
 
-def loss_and_grads(cfg, weights, x, x2, y_true, keep=1.0, key=0, l1=False, l2_decay=0.0, dtype=torch.float64):
+def loss_and_grads(cfg, weights, x, x2, y_true, keep=1.0, key=0, l1=False, l2_decay=0.0, dtype=torch.float64, taps=None):
     """(stats dict, {name: gradient as float64}) of loss = image_loss + l2_decay * sum 0.5 ||conv_W||^2; ``dtype`` float32
-    gives the same graph in torch float32 (the yardstick a failing parity test prints)."""
+    gives the same graph in torch float32 (the yardstick a failing parity test prints).  ``taps`` {conv variable prefix: anything},
+    when given, is filled with dict(z=pre-activation, out=the layer's output, dz=the loss gradient of z) per named layer, float64
+    numpy NHWC -- the tensors whose magnitudes option "train_split16" scales by."""
     leaves = {k: torch.tensor(np.asarray(v, np.float64), dtype=dtype, requires_grad=True) for k, v in weights.items()}
-    y = forward(cfg, leaves, x, x2, keep, key, dtype)
+    y = forward(cfg, leaves, x, x2, keep, key, dtype, taps)
     diff = y - torch.from_numpy(np.asarray(y_true, np.float64)).to(dtype).permute(0, 3, 1, 2)
     mse = torch.mean(diff * diff)
     image = torch.mean(torch.abs(diff)) if l1 else mse
@@ -99,6 +108,10 @@ def loss_and_grads(cfg, weights, x, x2, y_true, keep=1.0, key=0, l1=False, l2_de
     loss = image + l2_decay * l2
     loss.backward()
     grads = {k: v.grad.numpy().astype(np.float64) for k, v in leaves.items()}
+    if taps is not None:
+        nhwc = lambda a: a.detach().permute(0, 2, 3, 1).numpy().astype(np.float64)
+        for k, (z, out) in taps.items():
+            taps[k] = dict(z=nhwc(z), out=nhwc(out), dz=nhwc(z.grad))
     return dict(image_loss=image.item(), mse=mse.item(), loss=loss.item()), grads
 
 
