@@ -360,6 +360,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->train_split16 = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "train_split16_wgrad")) {      // any time, independent of "train_split16": re-carves in the same way
+        h->train_split16_wgrad = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
         h->p16 = value != 0;
         return DCSCN_OK;

@@ -13,6 +13,7 @@
 // the graph's variable list (dcscn_tensor_info), so the update is one elementwise launch.
 #include "plan.h"
 #include "train_h.hpp"
+#include "train_wgrad_h.hpp"
 
 #pragma clang fp contract(off)
 
@@ -483,6 +484,9 @@ struct TLayer {
     bool h16 = false;
     void *w16 = nullptr, *wd16 = nullptr;   // tpack_h images: forward, data gradient (null for a layer on the network input)
     int* e = nullptr;                       // exponents of the scales: [0] filter, [1] input slice, [2] dz
+    // option "train_split16_wgrad" (train_wgrad_h.hpp), in the current carve: the layer's weight gradient runs on tconv_wgrad_h; it reads
+    // e[1] and e[2], which the forward and the data gradient have found already when h16 is set as well
+    bool wg16 = false;
 };
 
 // the variables the l2 term sums over: the filters, not biases or prelu slopes
@@ -502,6 +506,7 @@ struct TrainState {
     void* arena = nullptr; size_t arena_bytes = 0;
     int n = 0, H = 0, W = 0;
     bool h16 = false;              // the carve holds the filter images and exponents of option "train_split16"
+    bool wg16 = false;             // ... the exponents and the partial sums of option "train_split16_wgrad"
     unsigned* absmax = nullptr;    // kAbsMaxBlocks partial maxima (launch_texp)
     float *dz = nullptr, *at = nullptr, *part = nullptr, *col = nullptr, *zlast = nullptr, *dzlast = nullptr, *clip = nullptr;
     float *io_x = nullptr, *io_x2 = nullptr, *io_y = nullptr;
@@ -607,8 +612,8 @@ static int col_splits(int64_t P, int64_t* chunk) {
 }
 
 static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
-    const bool h16 = h->train_split16;
-    if (t->arena && t->n == n && t->H == H && t->W == W && t->h16 == h16) return DCSCN_OK;
+    const bool h16 = h->train_split16, wg16 = h->train_split16_wgrad;
+    if (t->arena && t->n == n && t->H == H && t->W == W && t->h16 == h16 && t->wg16 == wg16) return DCSCN_OK;
     const int64_t P = (int64_t)n * H * W;
     size_t bytes = 0;
     auto take = [&](size_t floats) { size_t o = bytes; bytes += (floats * 4 + 255) / 256 * 256; return o; };
@@ -625,7 +630,8 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
         oz[l] = take((size_t)px * L.cout);
         dz_max = std::max(dz_max, (size_t)px * L.cout);
         int64_t ch;
-        const int s = wgrad_splits(L, px, &ch);
+        const int s = wg16 && tconv_h_eligible(L.cin, L.cout) ? twgrad_h_plan(L.ks, L.cin, L.cout, n, H * L.res, W * L.res).splits
+                                                              : wgrad_splits(L, px, &ch);
         part_max = std::max(part_max, (size_t)s * L.ks * L.ks * L.cin * L.cout);
         const int cs = col_splits(px, &ch);
         col_max = std::max(col_max, (size_t)cs * L.cout);
@@ -645,6 +651,8 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
             ow[l] = take(tpack_h_bytes(L.ks * L.ks, L.cin, L.cout) / 4);
             if (L.in_buf >= 0) owd[l] = take(tpack_h_bytes(L.ks * L.ks, L.cout, L.cin) / 4);
         }
+    }
+    if (h16 || wg16) {      // either option reads exponents
         o_exp = take(3 * t->layers.size());
         o_absmax = take(kAbsMaxBlocks);
     }
@@ -663,10 +671,11 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
         L.h16 = h16 && tconv_h_eligible(L.cin, L.cout);
         L.w16 = L.h16 ? base + ow[l] : nullptr;
         L.wd16 = L.h16 && L.in_buf >= 0 ? base + owd[l] : nullptr;
-        L.e = L.h16 ? (int*)(base + o_exp) + 3 * l : nullptr;
+        L.wg16 = wg16 && tconv_h_eligible(L.cin, L.cout);
+        L.e = L.h16 || L.wg16 ? (int*)(base + o_exp) + 3 * l : nullptr;
     }
-    t->h16 = h16;
-    t->absmax = h16 ? (unsigned*)(base + o_absmax) : nullptr;
+    t->h16 = h16; t->wg16 = wg16;
+    t->absmax = h16 || wg16 ? (unsigned*)(base + o_absmax) : nullptr;
     t->dz = (float*)(base + o_dz); t->at = (float*)(base + o_at); t->part = (float*)(base + o_part); t->col = (float*)(base + o_col);
     t->io_x = (float*)(base + o_x); t->io_x2 = (float*)(base + o_x2); t->io_y = (float*)(base + o_y); t->clip = (float*)(base + o_clip);
     t->dpart = (double*)(base + o_dpart);
@@ -693,10 +702,11 @@ static int launch_conv(dcscn_ctx* h, hipStream_t st, const float* in, int in_str
     return DCSCN_OK;
 }
 
-// the same conv on tconv_gemm_h (option "train_split16"): the exponent of the input's scale first, then the launch that reads it
+// the same conv on tconv_gemm_h (option "train_split16"): the exponent of the input's scale first (unless the caller has found it
+// already: find_e = false), then the launch that reads it
 static int launch_conv_h(dcscn_ctx* h, TrainState* t, hipStream_t st, const float* in, int in_stride, int cin, int n, int H, int W, int ks, const void* w16,
-                         const int* e_w, int* e_in, int cout, const float* bias, float* out, int out_stride, int accumulate) {
-    KTRY(h, launch_texp(in, in_stride, cin, (int64_t)n * H * W, t->absmax, e_in, st));
+                         const int* e_w, int* e_in, int cout, const float* bias, float* out, int out_stride, int accumulate, bool find_e = true) {
+    if (find_e) KTRY(h, launch_texp(in, in_stride, cin, (int64_t)n * H * W, t->absmax, e_in, st));
     TConvHArgs a{in, in_stride, cin, n, H, W, ks, w16, cout, bias, out, out_stride, e_in, e_w};
     KTRY(h, launch_tconv_gemm_h(a, accumulate, st));
     return DCSCN_OK;
@@ -775,11 +785,23 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
             KTRY(h, hipLaunchKernelGGL(td2s, dim3(grid1(px * L.cout)), dim3(256), 0, st, (const float*)t->dz, (float*)ob.g, n, Hr, Wr, L.ps, C, 1));
         }   // (the last layer: dz is the loss gradient already)
         // weight gradient (+ l2_decay * W)
-        int64_t chunk;
-        const int splits = wgrad_splits(L, px, &chunk);
         const int M = L.ks * L.ks * L.cin;
-        TWgradArgs wa{in, in_stride(L), L.cin, n, Hr, Wr, L.ks, t->dz, L.cout, chunk, t->part};
-        KTRY(h, hipLaunchKernelGGL(tconv_wgrad, dim3((M + 31) / 32, (L.cout + 31) / 32, splits), dim3(256), 0, st, wa));
+        int splits;
+        if (L.wg16) {
+            // e[1] is the forward's when the layer's convs run on tconv_gemm_h; e[2] is found here, once, for this launch and the data gradient's
+            if (!L.h16) KTRY(h, launch_texp(in, in_stride(L), L.cin, px, t->absmax, L.e + 1, st));
+            KTRY(h, launch_texp(t->dz, L.cout, L.cout, px, t->absmax, L.e + 2, st));
+            const TWgradHPlan wp = twgrad_h_plan(L.ks, L.cin, L.cout, n, Hr, Wr);
+            const TWgradHArgs wa{in, in_stride(L), L.cin, n, Hr, Wr, L.ks, t->dz, L.cout, L.e + 1, L.e + 2, t->part};
+            const hipError_t we = launch_tconv_wgrad_h(wa, wp, st);
+            if (we != hipSuccess) return fail(h, DCSCN_ERR_HIP, "tconv_wgrad_h (%s, %zu bytes of LDS): %s", L.name.c_str(), wp.lds_bytes, hipGetErrorString(we));
+            splits = wp.splits;
+        } else {
+            int64_t chunk;
+            splits = wgrad_splits(L, px, &chunk);
+            TWgradArgs wa{in, in_stride(L), L.cin, n, Hr, Wr, L.ks, t->dz, L.cout, chunk, t->part};
+            KTRY(h, hipLaunchKernelGGL(tconv_wgrad, dim3((M + 31) / 32, (L.cout + 31) / 32, splits), dim3(256), 0, st, wa));
+        }
         const int64_t wc = (int64_t)M * L.cout;
         KTRY(h, hipLaunchKernelGGL(treduce_wgrad, dim3(grid1(wc)), dim3(256), 0, st, (const float*)t->part, splits, wc, (const float*)(t->d_w + t->off[L.w_t]),
                                    (float)tc.l2_decay, t->d_g + t->off[L.w_t]));
@@ -796,7 +818,7 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         }
         // data gradient, accumulated into the input's gradient (none for the network input)
         if (gin) {
-            int rc = L.h16 ? launch_conv_h(h, t, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, L.wd16, L.e, L.e + 2, L.cin, nullptr, gin, in_stride(L), 1)
+            int rc = L.h16 ? launch_conv_h(h, t, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, L.wd16, L.e, L.e + 2, L.cin, nullptr, gin, in_stride(L), 1, !L.wg16)
                            : launch_conv(h, st, t->dz, L.cout, L.cout, n, Hr, Wr, L.ks, t->d_wd + t->off[L.w_t], L.cin, nullptr, gin, in_stride(L), 1);
             if (rc) return rc;
         }

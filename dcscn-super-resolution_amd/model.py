@@ -94,6 +94,8 @@ class SuperResolution:
         self.fast16 = bool(getattr(flags, "fast16", False))
         # extension: training takes the wide layers' forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16")
         self.train_split16 = bool(getattr(flags, "train_split16", False))
+        # extension: ... and their weight gradients (engine option "train_split16_wgrad"), independently
+        self.train_split16_wgrad = bool(getattr(flags, "train_split16_wgrad", False))
 
         # training parameters (DCSCN.py:50-93)
         fget = lambda k, d: getattr(flags, k, d)
@@ -395,6 +397,8 @@ class SuperResolution:
             eng.train_begin(self._train_flags)
             if self.train_split16:
                 eng.set_option("train_split16", 1)
+            if self.train_split16_wgrad:
+                eng.set_option("train_split16_wgrad", 1)
             self._train_engine = eng
             self._device_images = {}
             if self._pending_slots:

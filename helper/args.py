@@ -92,6 +92,8 @@ _TABLE = [
     (_B, "fast16", False, "inference at f16 operand accuracy: one matrix product per MAC instead of three (training is unaffected)"),
     # ---- extension (not a reference flag): training's wide forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16", include/dcscn.h)
     (_B, "train_split16", False, "training at f32 accuracy with the forward and data-gradient convs of layers with min(cin, cout) >= 16 as three scaled f16 products"),
+    # ---- extension (not a reference flag): the weight gradients of the same layers on the f16 matrix pipe (engine option "train_split16_wgrad", include/dcscn.h)
+    (_B, "train_split16_wgrad", False, "training at f32 accuracy with the weight gradients of layers with min(cin, cout) >= 16 as three scaled f16 products"),
     # ---- frozen graphs (args.py:97-98): weights from the Const nodes of a frozen GraphDef (dcscn-super-resolution_amd/frozen.py)
     (_B, "frozenInference", False, "Flag for whether the model to evaluate is frozen."),
     (_S, "frozen_graph_path", "./model_to_freeze/frozen_model_optimized.pb", "the path to a frozen model if performing inference from it"),

@@ -245,6 +245,16 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * and the mode has no redo flags and no float32 fallback; the epilogue undoes both scales with ldexp (exact).  A non-finite value in an
  * operand gives non-finite results, as on the f32 path.  Same parity bars as the default mode (1e-4 * max|g| per gradient tensor),
  * deterministic, but not the default mode's bits.  0 allocates and launches exactly what a handle that never set the option does.
+ * "train_split16_wgrad" (default 0; any time, also before dcscn_train_begin; takes effect from the next gradient computation, which
+ * re-carves the training workspace; independent of "train_split16": all four combinations are legal): with 1, every layer of the training
+ * plan with min(cin, cout) >= 16 -- the same rule of the shape -- takes its WEIGHT gradient on the f16 matrix pipe (tconv_wgrad_h): the sum
+ * over the pixels of in[p + tap][ci] * dz[p][co] as three f16 products ah * bh + ah * bl + al * bh per multiply-accumulate in chunks of 32
+ * pixels, accumulated in f32, both operands scaled by the power of two described above (found once per layer and step and shared with the
+ * "train_split16" convs when both options are on) and the scale undone with ldexp.  The pixels are summed over a fixed partition into tiles
+ * in a fixed order and the partial sums in split order, without atomics: deterministic, though not in the f32 kernel's order.  Narrower
+ * layers, the bias and PReLU-slope gradients, the l2 term and everything else are untouched: only the conv_W gradients of eligible layers
+ * (and with them the gradient norm) change bits.  Same parity bars as the default mode; a non-finite operand gives a non-finite result;
+ * 0 computes every bit of what a handle that never set the option computes, for either setting of "train_split16".
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The

@@ -6,7 +6,8 @@ Phases: forward (tconv_gemm<0>, tact_fwd, td2s), dgrad (tconv_gemm<1>, tpack_dgr
 tcol_*, tact_bwd), loss (tloss, tsumsq, tstats), optimizer (topt, tpowers).  td2s runs in both directions and is counted
 with the forward; tact_bwd (the activator and dropout backward) is counted with the weight gradient it feeds.  With option
 "train_split16" the eligible layers' convs are tconv_gemm_h<0> (forward) and tconv_gemm_h<1> (dgrad); what the option adds beside
-them -- tabsmax_part, texp_final, tpack_h -- is the phase "scale_pack".  "conv_kernels" lists the conv launches by kernel.
+them -- tabsmax_part, texp_final, tpack_h -- is the phase "scale_pack".  With option "train_split16_wgrad" the eligible layers' weight
+gradients are tconv_wgrad_h<taps> (phase wgrad, like tconv_wgrad), and its exponent reductions count with "scale_pack".  "conv_kernels" lists the conv launches by kernel.
 """
 import csv
 import glob

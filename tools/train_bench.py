@@ -21,6 +21,11 @@ plain run's handle (profiler runs of the option-on step).  --library PATH times 
 commit's, in a process of its own.
 
     python tools/train_bench.py --split16
+
+--split16-wgrad does the same with three handles, (train_split16, train_split16_wgrad) = (0, 0), (1, 0), (1, 1); --train-split16-wgrad
+sets the second option on the plain run's handle.
+
+    python tools/train_bench.py --split16-wgrad
 """
 import argparse
 import json
@@ -111,13 +116,53 @@ def bench_split16(name, n, size, steps, warmup):
                 min_ms=[round(float(np.min(times[0])), 4), round(float(np.min(times[1])), 4)])
 
 
-def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False):
+WGRAD_LEGS = ((0, 0), (1, 0), (1, 1))       # (train_split16, train_split16_wgrad)
+
+
+def bench_split16_wgrad(name, n, size, steps, warmup):
+    """(train_split16, train_split16_wgrad) = (0, 0), (1, 0), (1, 1) on three handles with the same weights and batch, alternating step
+    by step on one stream."""
+    from dcscn_amd import engine
+    cfg = O.make_config(**CONFIGS[name])
+    engs = []
+    for s16, wg in WGRAD_LEGS:
+        eng = engine.Engine(cfg, device=0)
+        eng.load_weights(O.synthetic_weights(cfg, seed=0))
+        eng.set_option("train_split16", s16)
+        eng.set_option("train_split16_wgrad", wg)
+        eng.train_begin(flags())
+        engs.append(eng)
+    x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, size, size))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    times = [[] for _ in engs]
+    for i in range(warmup + steps):
+        for k, eng in enumerate(engs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, size, size, 1e-4, i, stream=sp, want_stats=False)
+            b.record(stream)
+            b.synchronize()
+            if i >= warmup:
+                times[k].append(a.elapsed_time(b))
+    for eng in engs:
+        eng.close()
+    med = [float(np.median(t)) for t in times]
+    return dict(split16_wgrad_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, legs=[list(leg) for leg in WGRAD_LEGS],
+                ms=[round(m, 4) for m in med], min_ms=[round(float(np.min(t)), 4) for t in times],
+                ratio_11_over_10=round(med[2] / med[1], 4), ratio_11_over_00=round(med[2] / med[0], 4))
+
+
+def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wgrad=False):
     from dcscn_amd import engine
     eng = engine.Engine(cfg, device=0)
     eng.load_weights(O.synthetic_weights(cfg, seed=0))
     eng.train_begin(flags())
     if train_split16:
         eng.set_option("train_split16", 1)
+    if train_split16_wgrad:
+        eng.set_option("train_split16_wgrad", 1)
     x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, h, w))
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()          # a real stream: the events below are recorded where the steps run
@@ -250,6 +295,9 @@ def main():
     ap.add_argument("--device-only", action="store_true", help="--loop: the device-batch leg only (profiler runs)")
     ap.add_argument("--split16", action="store_true", help="time train_split16 = 0 and 1 alternating in one process (L12 x2, c-DCSCN x2)")
     ap.add_argument("--train-split16", action="store_true", help="set option train_split16 on the timed handle")
+    ap.add_argument("--split16-wgrad", action="store_true",
+                    help="time (train_split16, train_split16_wgrad) = (0, 0), (1, 0), (1, 1) alternating in one process (L12 x2, c-DCSCN x2)")
+    ap.add_argument("--train-split16-wgrad", action="store_true", help="set option train_split16_wgrad on the timed handle")
     ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
     if a.library:
@@ -259,6 +307,10 @@ def main():
         for name in ("L12_x2", "L7_x2"):
             print(json.dumps(bench_split16(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
         return
+    if a.split16_wgrad:
+        for name in ("L12_x2", "L7_x2"):
+            print(json.dumps(bench_split16_wgrad(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
+        return
     if a.loop:
         for name, n, size in LOOP_CASES:
             print(json.dumps(bench_loop(name, n, size, a.steps, a.warmup, a.device_only)), flush=True)
@@ -267,7 +319,7 @@ def main():
     if a.torch_only:
         print(json.dumps({"torch_ms_per_step": bench_torch(cfg, a.batch, a.size, a.size, a.steps, a.warmup)}))
         return
-    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup, a.train_split16)
+    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup, a.train_split16, a.train_split16_wgrad)
     flops = step_flops(cfg, a.batch, a.size, a.size)
     out = dict(config=a.config, batch=a.batch, lr_size=a.size, steps=a.steps, warmup=a.warmup, ms_per_step=round(med, 4),
                ms_per_step_min=round(best, 4), conv_gflop_per_step=round(flops / 1e9, 3),
