@@ -356,7 +356,11 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->fast16 = value != 0;
         return DCSCN_OK;
     }
-    if (!strcmp(key, "train_split16")) {            // any time: the next gradient computation re-carves the training arena (train.hip: carve)
+    if (!strcmp(key, "fast16_stream")) {            // any time, independent of "fast16": picks the instantiation of the feat3_stream launch
+        h->fast16_stream = value != 0;
+        return DCSCN_OK;
+    }
+    if (!strcmp(key, "train_split16")) {           // any time: the next gradient computation re-carves the training arena (train.hip: carve)
         h->train_split16 = value != 0;
         return DCSCN_OK;
     }

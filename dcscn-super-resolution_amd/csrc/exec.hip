@@ -178,7 +178,7 @@ static int launch_stream3(dcscn_ctx* h, const Op& op, const Pass& p) {
         for (size_t i = 0; i < op.extra_out.size(); ++i) a.out[i] = out_desc(op.extra_out[i], 0, -1);
     }
     a.redo = redo_flags(h);
-    HIP_TRY(h, stream3_launch(a, grid, p.stream));
+    HIP_TRY(h, stream3_launch(a, grid, p.stream, h->split16 && h->fast16_stream));
     return DCSCN_OK;
 }
 
@@ -662,6 +662,7 @@ int run_forward(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, 
     gkey.x = x; gkey.x2 = x2; gkey.y = y; gkey.stream = stream; gkey.n = n; gkey.H = H; gkey.W = W;
     gkey.split16 = h->split16 ? h->split16_mask : 0;
     gkey.fast16 = h->split16 && h->fast16 ? 1 : 0;       // (picks the instantiation of every layer-kernel launch)
+    gkey.fast16_stream = h->split16 && h->fast16_stream ? 1 : 0;      // (... and of the feat3_stream launch)
     gkey.nb = nb;                                        // the pass size (sub_batch_pixels / budget) shapes the launch sequence too
     gkey.h8 = h->conv3_h8 ? 1 : 0;
     gkey.nin_h8 = h->nin_h8 ? 1 : 0;

@@ -3,11 +3,12 @@
 
 namespace dcscn {
 
-hipError_t stream3_launch(const Stream3Args& a, int grid, hipStream_t stream) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&feat3_stream), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+hipError_t stream3_launch(const Stream3Args& a, int grid, hipStream_t stream, bool fast16) {
+    if (fast16) return stream3_fast16_launch(a, grid, stream);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&feat3_stream<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr != hipSuccess) return attr;
     if (a.n_waves < 2 || a.n_waves > kS3MaxWaves || a.ring_bytes > 160 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(feat3_stream, dim3(grid), dim3(a.n_waves * 64), (size_t)a.ring_bytes + 256, stream, a);
+    hipLaunchKernelGGL(feat3_stream<3>, dim3(grid), dim3(a.n_waves * 64), (size_t)a.ring_bytes + 256, stream, a);
     return hipGetLastError();
 }
 

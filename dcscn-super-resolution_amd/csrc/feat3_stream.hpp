@@ -18,6 +18,9 @@
 //   * wave -> SIMD placement balances the MFMA counts (pack.hip: pack_feat3_stream); CNN1 (one input channel) is VALU work on its own wave.
 //
 // The float32 plan of a flagged image, and split16 = 0, run the layers one by one on their own kernels (exec.hip: Op::fused).
+//
+// Option "fast16_stream" (NP = 1, feat3_stream_fast16.hip): every MFMA contraction of the launch as the single product fh * xh; CNN1, the blob,
+// the rings, the epilogues and the global tensors are those of the three-product form.
 #pragma once
 #include "feat_stream.hpp"
 #include "p16.hpp"
@@ -145,19 +148,27 @@ __device__ __forceinline__ void s3_first_role(const Stream3Args& a, const Stream
 // ds_read_b128 is 1 KB: ~250 of them per row step and workgroup), not by the MFMAs; the first build (one wave per output tile) read
 // them twice.  Split in a load part (filter fragments -> registers, for the whole launch) and a step part so that one wave can run
 // several light convs (s3_trio_role).
-template <int OCTS, int NT>
-struct S3ConvRegs {
+// NP = products per MAC (conv3_h.hpp): 3 = split16 (fl * xh + fh * xl + fh * xh); 1 = option "fast16_stream": fh * xh alone -- the lo filter
+// fragments do not exist (up to 72 registers of a wave), the lo units of the rings are not read and their MFMAs not issued; the bias rides
+// on the first fh * xh product.  Blob, rings, epilogues and global tensors are the same: they keep hi | lo.
+template <int STEPS, int NT, int NP>
+struct S3LoRegs { h8 fl[STEPS][NT]; };
+template <int STEPS, int NT>
+struct S3LoRegs<STEPS, NT, 1> {};
+template <int OCTS, int NT, int NP = 3>
+struct S3ConvRegs : S3LoRegs<(9 * OCTS + 3) / 4, NT, NP> {
+    static_assert(NP == 1 || NP == 3, "one product (fast16_stream) or three (split16)");
     static constexpr int STEPS = (9 * OCTS + 3) / 4;
-    h8 fh[STEPS][NT], fl[STEPS][NT];                           // [step][tile][hi | lo][64 lanes][8 halfs] in the blob
+    h8 fh[STEPS][NT];                                          // [step][tile][hi | lo][64 lanes][8 halfs] in the blob (fl: S3LoRegs)
     f32x4 bs[NT], am1[NT];                                     // bias * 2^e, slope - 1
     unsigned soff[OCTS == 1 ? STEPS : 1];
     unsigned dyp;
     StreamCursor cur;
 };
-template <int OCTS, int NT>
-__device__ __forceinline__ void s3_conv_load(const Stream3Args& a, int ci, int lane, S3ConvRegs<OCTS, NT>& r) {
+template <int OCTS, int NT, int NP>
+__device__ __forceinline__ void s3_conv_load(const Stream3Args& a, int ci, int lane, S3ConvRegs<OCTS, NT, NP>& r) {
     const S3Conv& c = a.conv[ci];
-    constexpr int STEPS = S3ConvRegs<OCTS, NT>::STEPS;
+    constexpr int STEPS = S3ConvRegs<OCTS, NT, NP>::STEPS;
     constexpr unsigned IN_PX = (unsigned)(2 * OCTS + 1) * 16u;
     const int q = lane >> 4;
     const char* wsrc = reinterpret_cast<const char*>(a.blob + c.w_off);
@@ -166,7 +177,7 @@ __device__ __forceinline__ void s3_conv_load(const Stream3Args& a, int ci, int l
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             r.fh[s][n] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((s * NT + n) * 2 + 0) * 64 + lane) * 16);
-            r.fl[s][n] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((s * NT + n) * 2 + 1) * 64 + lane) * 16);
+            if constexpr (NP == 3) r.fl[s][n] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((s * NT + n) * 2 + 1) * 64 + lane) * 16);
         }
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -194,12 +205,12 @@ __device__ __forceinline__ void s3_conv_load(const Stream3Args& a, int ci, int l
 // (Issuing the epilogue of row g - 1 between the MFMA groups of row g -- a software pipeline with the layers' lags spaced by three -- was
 // built and measured in r05: 0.83 ms against 0.66, the heaviest wave 7.8 k cycles per step instead of 6.0 k: the ring stores and the B-operand
 // reads share one in-order LGKM counter, and the waits for the one also wait for the other.)
-template <int OCTS, int NT>
+template <int OCTS, int NT, int NP>
 __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamArgs& geo, int ci, unsigned lds0, int j0, int rows, int t, int lane,
-                                             S3ConvRegs<OCTS, NT>& r, float m1, h2 zero2) {
+                                             S3ConvRegs<OCTS, NT, NP>& r, float m1, h2 zero2) {
     const S3Conv& c = a.conv[ci];
     const S3Out& og = a.out[ci + 1];
-    constexpr int STEPS = S3ConvRegs<OCTS, NT>::STEPS;
+    constexpr int STEPS = S3ConvRegs<OCTS, NT, NP>::STEPS;
     constexpr unsigned IN_PX = (unsigned)(2 * OCTS + 1) * 16u, IN_ROW = (unsigned)kStreamRowPx * IN_PX;
     const int j = lane & 15, q = lane >> 4;
     const unsigned out_px = (unsigned)c.out.px, out_row = (unsigned)kStreamRowPx * out_px;
@@ -229,20 +240,26 @@ __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamA
                     else base = (q >= thr ? rb[tb / 3] + (unsigned)offb : rb[ta / 3] + (unsigned)offa) + r.soff[0];
                 }
                 // the three pixel tiles' products interleaved: an accumulator is touched every third MFMA (back to back they wait for each other)
-                h8 xh[kStreamMT], xl[kStreamMT];
+                h8 xh[kStreamMT];
+                [[maybe_unused]] h8 xl[kStreamMT];
 #pragma unroll
                 for (int m = 0; m < kStreamMT; ++m) {
                     xh[m] = __builtin_bit_cast(h8, stream_ld(base + (unsigned)m * IN_PX));
-                    xl[m] = __builtin_bit_cast(h8, stream_ld(base + (unsigned)m * IN_PX + 16u));
+                    if constexpr (NP == 3) xl[m] = __builtin_bit_cast(h8, stream_ld(base + (unsigned)m * IN_PX + 16u));
                 }
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
+                    if constexpr (NP == 3) {
 #pragma unroll
-                    for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fl[s][n], xh[m], s == 0 ? r.bs[n] : acc[m][n], 0, 0, 0);
+                        for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fl[s][n], xh[m], s == 0 ? r.bs[n] : acc[m][n], 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fh[s][n], xl[m], acc[m][n], 0, 0, 0);
+                        for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fh[s][n], xl[m], acc[m][n], 0, 0, 0);
 #pragma unroll
-                    for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fh[s][n], xh[m], acc[m][n], 0, 0, 0);
+                        for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fh[s][n], xh[m], acc[m][n], 0, 0, 0);
+                    } else {
+#pragma unroll
+                        for (int m = 0; m < kStreamMT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r.fh[s][n], xh[m], s == 0 ? r.bs[n] : acc[m][n], 0, 0, 0);
+                    }
                 }
             });
             float chk = 0.0f;
@@ -273,31 +290,31 @@ __device__ __forceinline__ void s3_conv_step(const Stream3Args& a, const StreamA
             }
     }
 }
-template <int OCTS, int NT>
+template <int OCTS, int NT, int NP>
 __device__ __forceinline__ void s3_conv_role(const Stream3Args& a, const StreamArgs& geo, int ci, unsigned lds0, int j0, int rows, int T, int lane) {
-    S3ConvRegs<OCTS, NT> r;
-    s3_conv_load<OCTS, NT>(a, ci, lane, r);
+    S3ConvRegs<OCTS, NT, NP> r;
+    s3_conv_load<OCTS, NT, NP>(a, ci, lane, r);
     const float m1 = opaque_minus_one();
     const h2 zero2 = p16_opaque_zero2();
     for (int t = 0; t < T; ++t) {
-        s3_conv_step<OCTS, NT>(a, geo, ci, lds0, j0, rows, t, lane, r, m1, zero2);
+        s3_conv_step<OCTS, NT, NP>(a, geo, ci, lds0, j0, rows, t, lane, r, m1, zero2);
         stream_barrier();
     }
 }
 
 // ---- two light convs in ONE wave (nin.on: A1 || B1 takes two waves of the eight): they compute different stream rows of the same step, one
 // after the other.  c-DCSCN: (CNN6, CNN7) = 45 + 45 MFMAs and (CNN5, B2) = 63 + 27 against CNN2's 162 ------------------------------------
-template <int O1, int O2>
+template <int O1, int O2, int NP>
 __device__ __forceinline__ void s3_pair_role(const Stream3Args& a, const StreamArgs& geo, int c1, int c2, unsigned lds0, int j0, int rows, int T, int lane) {
-    S3ConvRegs<O1, 1> r1;
-    S3ConvRegs<O2, 1> r2;
-    s3_conv_load<O1, 1>(a, c1, lane, r1);
-    s3_conv_load<O2, 1>(a, c2, lane, r2);
+    S3ConvRegs<O1, 1, NP> r1;
+    S3ConvRegs<O2, 1, NP> r2;
+    s3_conv_load<O1, 1, NP>(a, c1, lane, r1);
+    s3_conv_load<O2, 1, NP>(a, c2, lane, r2);
     const float m1 = opaque_minus_one();
     const h2 zero2 = p16_opaque_zero2();
     for (int t = 0; t < T; ++t) {
-        s3_conv_step<O1, 1>(a, geo, c1, lds0, j0, rows, t, lane, r1, m1, zero2);
-        s3_conv_step<O2, 1>(a, geo, c2, lds0, j0, rows, t, lane, r2, m1, zero2);
+        s3_conv_step<O1, 1, NP>(a, geo, c1, lds0, j0, rows, t, lane, r1, m1, zero2);
+        s3_conv_step<O2, 1, NP>(a, geo, c2, lds0, j0, rows, t, lane, r2, m1, zero2);
         stream_barrier();
     }
 }
@@ -308,23 +325,24 @@ __device__ __forceinline__ void s3_pair_role(const Stream3Args& a, const StreamA
 // L = 7) -- with the slot of a row a compile-time constant of (step mod R, layer): the step loop is unrolled R times.  A layer is one K = 32 step (its
 // <= 4 octets; lane groups past the last octet re-read the last one against zero filters).  The row layer L - 1 completes is finished: scale,
 // PReLU, split; channels 0 .. 7 (B1) go to the B1 ring for B2 (s3_trio_role), channels 8 .. 31 (A1) to Concat2 behind B2's octet.
-template <int L>
+template <int L, int NP>
 __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamArgs& geo, int n, unsigned lds0, int j0, int rows, int T, int lane) {
     constexpr int R = 2 * L - 1;
     const int j = lane & 15, q = lane >> 4;
     // this wave's step is seven short dependent blocks (ring reads -> nine MFMAs): behind its SIMD partner's bursts of 27 - 54 MFMAs each of them
     // would wait; with priority its few MFMAs go first and the partner loses nothing it can measure
     asm volatile("s_setprio 1");
-    h8 fh[L], fl[L];
+    h8 fh[L];
+    [[maybe_unused]] h8 fl[NP == 3 ? L : 1];                       // (NP = 1: never touched)
     {
         const char* wsrc = reinterpret_cast<const char*>(a.blob + a.nin.w_off);
 #pragma unroll
         for (int i = 0; i < L; ++i) {
             fh[i] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((i * 2 + n) * 2 + 0) * 64 + lane) * 16);
-            fl[i] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((i * 2 + n) * 2 + 1) * 64 + lane) * 16);
+            if constexpr (NP == 3) fl[i] = *reinterpret_cast<const h8*>(wsrc + ((size_t)((i * 2 + n) * 2 + 1) * 64 + lane) * 16);
         }
     }
-    // (156 accumulator + 56 fragment registers: everything else is re-derived per step -- ring addresses from the lane, bias / slope from the blob)
+    // (156 accumulator + 56 fragment registers, 28 with NP = 1: everything else is re-derived per step -- ring addresses from the lane, bias / slope from the blob)
     const unsigned ba = lds0 + (unsigned)a.ring_bytes + (unsigned)(n * 16 + 4 * q) * 4u;    // bias * 2^e, slope - 1 at + 128 bytes: copied behind the rings at kernel start
     const float m1 = opaque_minus_one();
     const h2 zero2 = p16_opaque_zero2();
@@ -345,20 +363,26 @@ __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamAr
                 const int qq = qe < rg.octs ? qe : rg.octs - 1;      // (octets past the layer's last: any valid unit of the pixel, the filter rows are zero)
                 const unsigned px = (unsigned)rg.px;
                 const unsigned b = lds0 + (unsigned)rg.off + ((unsigned)(g & 3) * (unsigned)kStreamRowPx + (unsigned)(3 * je + 1)) * px + (unsigned)qq * 32u;
-                h8 xh[kStreamMT], xl[kStreamMT];
+                h8 xh[kStreamMT];
+                [[maybe_unused]] h8 xl[kStreamMT];
 #pragma unroll
                 for (int m = 0; m < kStreamMT; ++m) {
                     xh[m] = __builtin_bit_cast(h8, stream_ld(b + (unsigned)m * px));
-                    xl[m] = __builtin_bit_cast(h8, stream_ld(b + (unsigned)m * px + 16u));
+                    if constexpr (NP == 3) xl[m] = __builtin_bit_cast(h8, stream_ld(b + (unsigned)m * px + 16u));
                 }
                 f32x4 bs = kStreamZero;
                 if constexpr (i == 0) bs = stream_ld(ba);
+                if constexpr (NP == 3) {
 #pragma unroll
-                for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[i], xh[m], i == 0 ? bs : acc[s][m], 0, 0, 0);
+                    for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[i], xh[m], i == 0 ? bs : acc[s][m], 0, 0, 0);
 #pragma unroll
-                for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], xl[m], acc[s][m], 0, 0, 0);
+                    for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], xl[m], acc[s][m], 0, 0, 0);
 #pragma unroll
-                for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], xh[m], acc[s][m], 0, 0, 0);
+                    for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], xh[m], acc[s][m], 0, 0, 0);
+                } else {
+#pragma unroll
+                    for (int m = 0; m < kStreamMT; ++m) acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], xh[m], i == 0 ? bs : acc[s][m], 0, 0, 0);
+                }
             }
         });
         constexpr int sl = ((p - 2 * (L - 1) - 1) % R + R) % R;
@@ -390,6 +414,8 @@ __device__ __forceinline__ void s3_nin_role(const Stream3Args& a, const StreamAr
 }
 
 // one workgroup = n_waves <= 8 waves (CNN1 + one per conv; pack.hip: the role table), one per CU (the rings take most of the LDS)
+// (NP = 3: feat3_stream.hip; NP = 1: feat3_stream_fast16.hip)
+template <int NP = 3>
 __global__ __launch_bounds__(512) void feat3_stream(const Stream3Args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -411,16 +437,16 @@ __global__ __launch_bounds__(512) void feat3_stream(const Stream3Args a) {
     else if (ci >= kS3RolePair) {
         // (instantiated for the c-DCSCN shape; graph.hip: fuse_feat3_stream checks: pair 0 = conv[L - 3], conv[L - 2] reading two octets each,
         //  pair 1 = conv[L - 4] reading three octets and B2 = conv[L - 1] reading B1's one)
-        if (ci == kS3RolePair) s3_pair_role<2, 2>(a, geo, a.L - 3, a.L - 2, lds0, j0, rows, T, lane);
-        else s3_pair_role<3, 1>(a, geo, a.L - 4, a.L - 1, lds0, j0, rows, T, lane);
-    } else if (ci >= kS3RoleNin) s3_nin_role<7>(a, geo, ci - kS3RoleNin, lds0, j0, rows, T, lane);
+        if (ci == kS3RolePair) s3_pair_role<2, 2, NP>(a, geo, a.L - 3, a.L - 2, lds0, j0, rows, T, lane);
+        else s3_pair_role<3, 1, NP>(a, geo, a.L - 4, a.L - 1, lds0, j0, rows, T, lane);
+    } else if (ci >= kS3RoleNin) s3_nin_role<7, NP>(a, geo, ci - kS3RoleNin, lds0, j0, rows, T, lane);
     else {
         const bool two = a.conv[ci].tiles == 2;
         switch (a.conv[ci].in.octs) {
-            case 1: if (two) s3_conv_role<1, 2>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<1, 1>(a, geo, ci, lds0, j0, rows, T, lane); break;
-            case 2: if (two) s3_conv_role<2, 2>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<2, 1>(a, geo, ci, lds0, j0, rows, T, lane); break;
-            case 3: if (two) s3_conv_role<3, 2>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<3, 1>(a, geo, ci, lds0, j0, rows, T, lane); break;
-            default: if (two) s3_conv_role<4, 2>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<4, 1>(a, geo, ci, lds0, j0, rows, T, lane); break;
+            case 1: if (two) s3_conv_role<1, 2, NP>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<1, 1, NP>(a, geo, ci, lds0, j0, rows, T, lane); break;
+            case 2: if (two) s3_conv_role<2, 2, NP>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<2, 1, NP>(a, geo, ci, lds0, j0, rows, T, lane); break;
+            case 3: if (two) s3_conv_role<3, 2, NP>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<3, 1, NP>(a, geo, ci, lds0, j0, rows, T, lane); break;
+            default: if (two) s3_conv_role<4, 2, NP>(a, geo, ci, lds0, j0, rows, T, lane); else s3_conv_role<4, 1, NP>(a, geo, ci, lds0, j0, rows, T, lane); break;
         }
     }
 }

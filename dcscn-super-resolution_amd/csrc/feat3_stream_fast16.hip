@@ -1,0 +1,14 @@
+// feat3_stream with ONE product per MAC (feat3_stream.hpp: NP = 1; option "fast16_stream"), one translation unit to parallelise the build.
+#include "feat3_stream.hpp"
+
+namespace dcscn {
+
+hipError_t stream3_fast16_launch(const Stream3Args& a, int grid, hipStream_t stream) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&feat3_stream<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (attr != hipSuccess) return attr;
+    if (a.n_waves < 2 || a.n_waves > kS3MaxWaves || a.ring_bytes > 160 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(feat3_stream<1>, dim3(grid), dim3(a.n_waves * 64), (size_t)a.ring_bytes + 256, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace dcscn

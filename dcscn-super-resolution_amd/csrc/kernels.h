@@ -295,7 +295,9 @@ struct Stream3Args {
     int32_t ring_bytes;
     int32_t* redo;                 // [0] pass flag, [1 + image] (split16.hpp)
 };
-hipError_t stream3_launch(const Stream3Args& a, int grid, hipStream_t stream);
+// fast16 (option "fast16_stream"): the one-product instantiation (feat3_stream.hpp: NP = 1) on the same arguments
+hipError_t stream3_launch(const Stream3Args& a, int grid, hipStream_t stream, bool fast16 = false);
+hipError_t stream3_fast16_launch(const Stream3Args& a, int grid, hipStream_t stream);      // feat3_stream_fast16.hip
 
 // widest channel tile (in units of 16) the fused-depthwise pointwise kernels are instantiated for
 int conv_max_fused_dw_nt();

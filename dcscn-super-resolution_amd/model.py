@@ -92,6 +92,8 @@ class SuperResolution:
         self.device_metrics = bool(getattr(flags, "device_metrics", False))
         # extension: forwards take one f16 product per MAC (engine option "fast16"; set on every engine this model creates)
         self.fast16 = bool(getattr(flags, "fast16", False))
+        # extension: ... and the streamed feature extractor of the narrow nets too (engine option "fast16_stream"), independently
+        self.fast16_stream = bool(getattr(flags, "fast16_stream", False))
         # extension: training takes the wide layers' forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16")
         self.train_split16 = bool(getattr(flags, "train_split16", False))
         # extension: ... and their weight gradients (engine option "train_split16_wgrad"), independently
@@ -210,6 +212,8 @@ class SuperResolution:
         self._engine = engine.Engine(self._engine_config(), device=self.gpu_device_id)
         if self.fast16:
             self._engine.set_option("fast16", 1)
+        if self.fast16_stream:
+            self._engine.set_option("fast16_stream", 1)
         self._weights = None
         return self._engine
 

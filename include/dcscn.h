@@ -227,12 +227,22 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * both (a later fast16 = 0, or a launch that keeps three products, reads them as before), the 2^-e scale, bias, activators and the residual
  * add run in f32, and the redo flags and the gated float32 plan work as described under "split16" -- a flagged image is still recomputed to
  * the bits of a split16 = 0 run, bystanders keep their fast16 bits.  The streamed kernels (feat_stream, tail_stream, feat3_stream) keep
- * three products, so the narrow nets change only in their folded tail; split16 = 0 ignores the option.
+ * three products under this option (feat3_stream has its own: "fast16_stream" below), so the narrow nets change only in their folded
+ * tail; split16 = 0 ignores the option.
  * Error against the float64 oracle on the 0-255 scale (seeded weights, U(0, 255) input), CPU model of the mode: max-abs 2.2e-3, rms 5.6e-4
  * for L12 x2, 3.7e-3 / 9.4e-4 for L12 x4, 2.6e-3 / 8.3e-4 for L8 x2, 1.5e-3 / 4.4e-4 for c-DCSCN x2 -- about a hundred times split16's
  * 1.5e-5 and 1/200 of an 8-bit step.  Measured on an MI355X: 2.3e-3 / 6.2e-4 (L12 x2), 3.1e-3 / 8.0e-4 (L12 x4), 3.5e-3 / 8.7e-4 (L8 x2);
  * with the shipped c-DCSCN x2 weights, layer by layer, 1.3e-2 / 1.5e-3.  A 1024-patch pass of L12 x2 takes 0.667 of its time (DESIGN.md
  * 3.13).  Not f32 accuracy, not bf16 / fp8, not for training.
+ * "fast16_stream" (default 0; any time, like "fast16", and independent of it: all four combinations are legal): the same mode for the
+ * feat3_stream launch of the non-separable narrow nets (c-DCSCN), which "fast16" leaves on three products.  With 1, every matrix
+ * contraction inside that launch -- CNN2 .. CNNL and, where "stream_nin" puts them there, A1 || B1 and B2 -- is the single product
+ * wh * xh: the `hi` piece of the ring unit, which is f16(x), times the `hi` piece of the scaled filter image, accumulated in f32; the
+ * `lo` filter fragments are not loaded, the `lo` ring units not read and their two products not issued.  CNN1 stays f32 VALU work, the
+ * filter blob still holds (hi | lo), epilogues still write (hi | lo) units to the rings and to global memory (conv_nin_h behind
+ * stream_nin = 0, the tail kernels and a later fast16_stream = 0 read what they always read), and scale, bias, PReLU, the redo flags and
+ * the gated float32 plan are split16's.  Ignored where the plan has no feat3_stream launch: split16 = 0, stream_dense = 0, the wide nets,
+ * and the separable nets' feat_stream / tail_stream, which keep three products.  Error and speed: DESIGN.md 3.13.
  * "train_split16" (default 0; any time, also before dcscn_train_begin; takes effect from the next gradient computation, which re-carves
  * the training workspace): an opt-in training mode at the f32 path's accuracy.  With 1, every layer of the training plan with
  * min(cin, cout) >= 16 -- a rule of the layer's shape alone, the same for both directions -- takes its forward conv and its data-gradient

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Throughput of the other BASELINE.json configurations (bench.py measures configs[2]):
    python tools/bench_configs.py [--steps 5]   -> one line per config, per-launch table with --ops.
-   --fast16: every config is timed with option fast16 = 0 and 1 ALTERNATING in one process (--rounds blocks of --steps passes each,
-   median block per setting), one line per setting plus their ratio; with --ops the per-launch times of both settings side by side."""
+   --fast16: every config is timed with the options (fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) ALTERNATING in one process
+   (--rounds blocks of --steps passes each, median block per setting), one line per setting plus their ratios; with --ops the per-launch
+   times of the settings side by side and the feat3_stream launch's own time per setting."""
 import argparse
 import os
 import sys
@@ -22,22 +23,35 @@ CONFIGS = [
     ("L7 dcscn_L7_F32to8 x2 (c-DCSCN), 1024 patches", dict(L7), 1024),
     ("L7x3 dcscn_L7_F32to8 x3 (c-DCSCN), 1024 patches", dict(L7, scale=3), 1024),
     ("L7x4 dcscn_L7_F32to8 x4 (c-DCSCN), 1024 patches", dict(L7, scale=4), 1024),
+    ("L8n dcscn_L8_F32to1 G1.5 x2 (octets 4 .. 1), 1024 patches", dict(L7, layers=8, min_filters=1, filters_decay_gamma=1.5), 1024),
 ]
 
 
+SETTINGS = ((0, 0), (1, 0), (0, 1), (1, 1))           # (fast16, fast16_stream)
+
+
+def _set(eng, setting):
+    eng.set_option("fast16", setting[0])
+    eng.set_option("fast16_stream", setting[1])
+
+
 def fast16_compare(args, name, eng, torch, io):
-    """fast16 = 0 and 1 in alternating blocks of args.steps passes on one handle; median block per setting."""
+    """(fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) in alternating blocks of args.steps passes on one handle; median block per
+    setting.  A plan without a feat3_stream launch ignores fast16_stream: only the first two settings are timed there."""
     x, x2, y, n, st = io
     run = lambda: eng.forward_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, 48, 48, st)
-    for v in (0, 1):                                   # warm both settings (and capture both graphs with --graph)
-        eng.set_option("fast16", v)
+    streamed = [i for i, o in enumerate(eng.ops()) if o["kernel"] == "feat3_stream"]
+    settings = SETTINGS if streamed else SETTINGS[:2]
+    tag = lambda v: "fast16 %d fast16_stream %d" % v
+    for v in settings:                                 # warm every setting (and capture its graph with --graph)
+        _set(eng, v)
         for _ in range(3):
             run()
     torch.cuda.synchronize()
-    times = {0: [], 1: []}
+    times = {v: [] for v in settings}
     for _ in range(args.rounds):
-        for v in (0, 1):
-            eng.set_option("fast16", v)
+        for v in settings:
+            _set(eng, v)
             run()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -46,25 +60,34 @@ def fast16_compare(args, name, eng, torch, io):
             torch.cuda.synchronize()
             times[v].append((time.perf_counter() - t0) / args.steps * 1e3)
     med = {v: sorted(t)[len(t) // 2] for v, t in times.items()}
-    for v in (0, 1):
-        print("%-48s fast16 %d  %8.3f ms/step median of %d blocks (min %.3f max %.3f)" % (name, v, med[v], args.rounds, min(times[v]), max(times[v])), flush=True)
-    print("%-48s fast16 1 / fast16 0 = %.4f" % (name, med[1] / med[0]), flush=True)
+    for v in settings:
+        print("%-48s %s  %8.3f ms/step median of %d blocks (min %.3f max %.3f)" % (name, tag(v), med[v], args.rounds, min(times[v]), max(times[v])), flush=True)
+    print("%-48s (1,0) / (0,0) = %.4f" % (name, med[(1, 0)] / med[(0, 0)]), flush=True)
+    if streamed:
+        print("%-48s (0,1) / (0,0) = %.4f   (1,1) / (1,0) = %.4f   (1,1) / (0,0) = %.4f" % (
+            name, med[(0, 1)] / med[(0, 0)], med[(1, 1)] / med[(1, 0)], med[(1, 1)] / med[(0, 0)]), flush=True)
     if args.ops and not args.graph:
         per = {}
         eng.set_option("profile", 1)
-        for v in (0, 1):
-            eng.set_option("fast16", v)
-            rows = []
-            for _ in range(args.steps):
+        rows = {v: [] for v in settings}
+        for _ in range(args.steps):                    # alternating here too: one profiled pass per setting and round
+            for v in settings:
+                _set(eng, v)
                 run()
                 torch.cuda.synchronize()
-                rows.append(eng.profile())
-            per[v] = [sorted(c)[len(c) // 2] for c in zip(*rows)]
+                rows[v].append(eng.profile())
+        for v in settings:
+            per[v] = [sorted(c)[len(c) // 2] for c in zip(*rows[v])]
         eng.set_option("profile", 0)
-        for o, a, b in zip(eng.ops(), per[0], per[1]):
-            print("    %-26s %-11s k%d %4d->%-4d res%d  fast16 0 %8.3f ms  fast16 1 %8.3f ms  ratio %.3f" % (
-                o["name"], o["kernel"], o["kernel_size"], o["in_channels"], o["out_channels"], o["resolution"], a, b, b / a if a else 0))
-        print("    %-26s fast16 0 %8.3f ms  fast16 1 %8.3f ms" % ("sum of launches", sum(per[0]), sum(per[1])), flush=True)
+        for i, o in enumerate(eng.ops()):
+            base = per[settings[0]][i]
+            print("    %-26s %-12s k%d %4d->%-4d res%d  " % (o["name"], o["kernel"], o["kernel_size"], o["in_channels"], o["out_channels"], o["resolution"])
+                  + "  ".join("(%d,%d) %7.3f ms" % (v + (per[v][i],)) for v in settings)
+                  + "  ratio to (0,0) " + " ".join("%.3f" % (per[v][i] / base if base else 0) for v in settings[1:]))
+        print("    %-26s " % "sum of launches" + "  ".join("(%d,%d) %7.3f ms" % (v + (sum(per[v]),)) for v in settings), flush=True)
+        for i in streamed:                             # the streamed launch's own time per setting
+            print("    feat3_stream launch %-22s " % eng.ops()[i]["name"] + "  ".join("(%d,%d) %7.3f ms" % (v + (per[v][i],)) for v in settings)
+                  + "  (0,1) / (0,0) = %.4f  (1,1) / (1,0) = %.4f" % (per[(0, 1)][i] / per[(0, 0)][i], per[(1, 1)][i] / per[(1, 0)][i]), flush=True)
 
 
 def main():
@@ -73,7 +96,7 @@ def main():
     ap.add_argument("--ops", action="store_true")
     ap.add_argument("--only", default="")
     ap.add_argument("--graph", action="store_true", help="option graph_replay: the pass replayed from a hipGraph")
-    ap.add_argument("--fast16", action="store_true", help="time fast16 = 0 and 1 alternating in one process and print the ratio")
+    ap.add_argument("--fast16", action="store_true", help="time (fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) alternating in one process and print the ratios")
     ap.add_argument("--rounds", type=int, default=7, help="--fast16: timed blocks per setting")
     args = ap.parse_args()
     import torch
