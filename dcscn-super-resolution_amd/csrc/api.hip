@@ -209,14 +209,14 @@ int dcscn_finalize(dcscn_handle h) {
         if (op.kind == OP_CONV && op.shape.nin && op.h16.on && op.h16.in16_ok) {
             // conv_nin_h with P16 sources: 4 octet entries per 32-channel chunk
             op.h16.h_tab16.assign((size_t)4 * op.h16.n_chunks, NinSrcQuad{0, 0, 0});
-            rc = upload(h, op.h16.h_tab16.data(), op.h16.h_tab16.size() * sizeof(NinSrcQuad), (void**)&op.h16.d_tab16);
+            rc = upload_vec(h, op.h16.h_tab16, &op.h16.d_tab16);
             if (rc) return rc;
         }
         auto alloc_srctab = [&](Op& o) {
             if (o.multi.empty()) return (int)DCSCN_OK;
             // 4 quads per 16-channel chunk of conv_nin; conv_nin_h walks the same table 8 quads per 32-channel chunk
             o.h_srctab.assign(std::max<size_t>((size_t)4 * o.n_chunks, (size_t)8 * ((o.cin_phys + kNinHKC - 1) / kNinHKC)), NinSrcQuad{0, 0, 0});
-            return upload(h, o.h_srctab.data(), o.h_srctab.size() * sizeof(NinSrcQuad), (void**)&o.d_srctab);
+            return upload_vec(h, o.h_srctab, &o.d_srctab);
         };
         rc = alloc_srctab(op);
         if (rc) return rc;

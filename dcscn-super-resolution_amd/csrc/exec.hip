@@ -727,8 +727,8 @@ int resample_table(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::Res
         std::vector<double> kk;
         dcscn_ctx::ResampleTable t;
         t.ksize = resample_coeffs(in_size, out_size, &bounds, &kk);
-        int rc = upload(h, bounds.data(), bounds.size() * sizeof(int), (void**)&t.d_bounds);
-        if (!rc) rc = upload(h, kk.data(), kk.size() * sizeof(double), (void**)&t.d_kk);
+        int rc = upload_vec(h, bounds, &t.d_bounds);
+        if (!rc) rc = upload_vec(h, kk, &t.d_kk);
         if (rc) return rc;
         it = h->resample_tables.emplace(key, t).first;
     }

@@ -201,7 +201,7 @@ struct StreamNinSrc {     // one feature layer as a K-slice of A1 || B1
 struct StreamArgs {
     const float* x;       // [N, H, W] luma
     float* out;           // Concat2 [N, H, W, out_stride]: B2 at channel 0, A1 at channel 4 * nb_quads
-    const float* blob;    // packed parameters (api.hip: pack_feat_stream)
+    const float* blob;    // packed parameters (pack.hip: pack_feat_stream)
     int32_t out_stride;
     int32_t N, H, W;
     int32_t n_strips, useful_w, halo;      // strip s computes columns [s * useful_w - halo, .. + 48), stores [s * useful_w, (s + 1) * useful_w)
@@ -230,7 +230,7 @@ struct TailArgs {
     const float* c2;      // Concat2 [N, H, W, c2_stride]
     const float* x2;      // bicubic image [N, 4H, 4W]
     float* y;             // [N, 4H, 4W]
-    const float* blob;    // LDS image of the filters (api.hip: pack_tail_stream)
+    const float* blob;    // LDS image of the filters (pack.hip: pack_tail_stream)
     int32_t c2_stride;
     int32_t N, H, W;
     int32_t n_strips, useful_w, halo;

@@ -1,6 +1,6 @@
 // Internal interface of the plan / ABI layer: the handle, the launch plan (Op) and the functions its translation units share.
 //   graph.hip  build_graph (DCSCN.py:222-325 as a list of launches), graph rewrites (folded tail, streamed nets, dense features)
-//   pack.hip   filter repacking into the LDS images of the kernels (finalize_op and the streamed-kernel blobs)
+//   pack.hip   filter repacking into the LDS images of the kernels (finalize_op dispatches to one packer per kind of launch)
 //   exec.hip   workspace, launches, sub-batching, spatial tiling, resize
 //   api.hip    the extern "C" surface of include/dcscn.h
 #pragma once
@@ -302,6 +302,8 @@ void plan_p16(dcscn_ctx* h);
 inline bool p16_active(const dcscn_ctx* h) { return h->p16 && h->any_p16 && h->split16 && h->split16_mask == 3; }
 // pack.hip
 int upload(dcscn_ctx* h, const void* host, size_t bytes, void** dev);
+template <class T, class P>
+inline int upload_vec(dcscn_ctx* h, const std::vector<T>& v, P** dev) { return upload(h, v.data(), v.size() * sizeof(T), (void**)dev); }
 int finalize_op(dcscn_ctx* h, Op& op);
 int pack_feat_stream(dcscn_ctx* h, Op& op);
 int pack_tail_stream(dcscn_ctx* h, Op& op);

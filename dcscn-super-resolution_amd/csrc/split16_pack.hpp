@@ -60,26 +60,6 @@ inline int split16_scale_exp(const float* w, size_t n) {
     return 14 - ex;
 }
 
-// conv_nin_h image: dense [k_rows][cols] (k_rows = n_chunks * 16 physical input channels, cols = n_groups * nt * 16 padded
-// output channels) -> [group][chunk][n][lane = kq * 16 + i][hi0..3, lo0..3] halfs: the A fragments of
-// v_mfma_f32_16x16x16_f16 (row i = output channel, k = 4 kq + t), one 16-byte LDS read per lane and tile.
-inline std::vector<uint16_t> pack_nin16(const std::vector<float>& dense, int k_rows, int cols, int n_groups, int nt, int n_chunks, int scale_exp) {
-    std::vector<uint16_t> out((size_t)n_groups * n_chunks * nt * 64 * 8, 0);
-    for (int g = 0; g < n_groups; ++g)
-        for (int c = 0; c < n_chunks; ++c)
-            for (int n = 0; n < nt; ++n)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int i = lane & 15, kq = lane >> 4;
-                    uint16_t* dst = &out[((((size_t)g * n_chunks + c) * nt + n) * 64 + lane) * 8];
-                    for (int t = 0; t < 4; ++t) {
-                        const int k = c * 16 + 4 * kq + t, col = (g * nt + n) * 16 + i;
-                        const float w = k < k_rows ? dense[(size_t)k * cols + col] : 0.0f;
-                        split16_host(std::ldexp(w, scale_exp), &dst[t], &dst[4 + t]);
-                    }
-                }
-    return out;
-}
-
 // conv3_h image: dense [tap][k_rows][cols] -> [group][chunk of 32 channels][tap][n][part: 0 hi, 1 lo][lane = kq * 16 + i][8 halfs]:
 // the A fragments of v_mfma_f32_16x16x32_f16 (row i = output channel, k = 8 kq + t).
 // tail_octs = 1 / 2 / 3 (conv3_h's packed last chunk, taps == 9): the last chunk holds at most 8 / 16 / 24 real channels, so its

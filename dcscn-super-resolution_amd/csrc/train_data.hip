@@ -138,7 +138,7 @@ int resample_table8(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::Re
         std::vector<int> k8(kk.size());
         for (size_t i = 0; i < kk.size(); ++i)
             k8[i] = kk[i] < 0 ? (int)(-0.5 + kk[i] * (1 << kPrecisionBits)) : (int)(0.5 + kk[i] * (1 << kPrecisionBits));
-        if ((rc = upload(h, k8.data(), k8.size() * sizeof(int), (void**)&e.d_k8))) return rc;
+        if ((rc = upload_vec(h, k8, &e.d_k8))) return rc;
     }
     *out = &e;
     return DCSCN_OK;
