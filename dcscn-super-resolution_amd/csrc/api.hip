@@ -522,6 +522,65 @@ int dcscn_resize_bicubic_device(dcscn_handle h, const float* in, float* out, int
     return forward_done(h, st);
 }
 
+int dcscn_resample_table_bytes(int in_size, int out_size, int* ksize, int* bounds, int32_t* coeffs, int capacity) {
+    if (in_size <= 0 || out_size <= 0 || !ksize) return DCSCN_ERR_INVALID_ARG;
+    std::vector<int> b, k;
+    *ksize = resample_coeffs8(in_size, out_size, &b, &k);
+    if (!bounds && !coeffs) return DCSCN_OK;                        // size query
+    if (!bounds || !coeffs || capacity < (int)k.size()) return DCSCN_ERR_INVALID_ARG;
+    std::copy(b.begin(), b.end(), bounds);
+    std::copy(k.begin(), k.end(), coeffs);
+    return DCSCN_OK;
+}
+
+// the shared argument checks of the two uint8 resizes; *run = there is something to do
+static int resize_bytes_args(dcscn_handle h, const uint8_t* in, uint8_t* out, int n, int height, int width, int channels, int out_height,
+                             int out_width, bool* run) {
+    *run = false;
+    if (n < 0 || height <= 0 || width <= 0 || out_height <= 0 || out_width <= 0)
+        return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape n=%d %dx%d -> %dx%d", n, height, width, out_height, out_width);
+    if (channels != 1 && channels != 3)
+        return fail(h, DCSCN_ERR_INVALID_ARG, "%d channels (uint8 images have 1 (mode L) or 3 (RGB))", channels);
+    if (n == 0) return DCSCN_OK;
+    if (!in || !out) return fail(h, DCSCN_ERR_INVALID_ARG, "null image pointer");
+    *run = true;
+    return DCSCN_OK;
+}
+
+int dcscn_resize_bicubic_bytes(dcscn_handle h, const uint8_t* in, uint8_t* out, int n, int height, int width, int channels, int out_height,
+                               int out_width) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    bool run;
+    int rc = resize_bytes_args(h, in, out, n, height, width, channels, out_height, out_width, &run);
+    if (rc || !run) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t ni = (size_t)n * height * width * channels, no = (size_t)n * out_height * out_width * channels;
+    rc = grow(h, &h->rs_in, &h->rs_in_cap, (ni + 3) / 4, h->stream);
+    if (!rc) rc = grow(h, &h->rs_out, &h->rs_out_cap, (no + 3) / 4, h->stream);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpy(h->rs_in, in, ni, hipMemcpyHostToDevice));
+    rc = resize_device_bytes(h, reinterpret_cast<const uint8_t*>(h->rs_in), reinterpret_cast<uint8_t*>(h->rs_out), n, height, width, channels,
+                             out_height, out_width, h->stream);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(out, h->rs_out, no, hipMemcpyDeviceToHost));
+    return DCSCN_OK;
+}
+
+int dcscn_resize_bicubic_bytes_device(dcscn_handle h, const uint8_t* in, uint8_t* out, int n, int height, int width, int channels,
+                                      int out_height, int out_width, void* stream) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    bool run;
+    int rc = resize_bytes_args(h, in, out, n, height, width, channels, out_height, out_width, &run);
+    if (rc || !run) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;                          // ordered as dcscn_resize_bicubic_device
+    if (h->has_last && h->last_stream != st) HIP_TRY(h, hipStreamWaitEvent(st, h->done_ev, 0));
+    rc = resize_device_bytes(h, in, out, n, height, width, channels, out_height, out_width, st);
+    if (rc) return rc;
+    return forward_done(h, st);
+}
+
 int dcscn_forward_lr(dcscn_handle h, const float* x, float* y, int n, int height, int width) {
     if (!h) return DCSCN_ERR_INVALID_ARG;
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_forward_lr before dcscn_finalize");
@@ -827,6 +886,51 @@ int dcscn_sr_rgb(dcscn_handle h, const uint8_t* rgb, const uint8_t* rgb_upscaled
     else HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (rc) return rc;
     HIP_TRY(h, hipMemcpy(rgb_out, h->col_d2, 3 * hr * sizeof(double), hipMemcpyDeviceToHost));
+    return DCSCN_OK;
+}
+
+int dcscn_sr_rgb_bytes(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, uint8_t* rgb_bicubic, uint8_t* y_bicubic,
+                       uint8_t* y_out, uint8_t* rgb_out) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_sr_rgb_bytes before dcscn_finalize");
+    if (int rc_ = train_sync_inference(h)) return rc_;
+    if (!rgb || (!rgb_bicubic && !y_bicubic && !y_out && !rgb_out)) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_sr_rgb_bytes: null pointer");
+    if (n_ensemble < 1 || n_ensemble > 8) return fail(h, DCSCN_ERR_INVALID_ARG, "n_ensemble %d outside [1, 8]", n_ensemble);
+    if (height <= 0 || width <= 0) return fail(h, DCSCN_ERR_INVALID_ARG, "bad shape h=%d w=%d", height, width);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int s = h->cfg.scale;
+    const size_t lrn = (size_t)height * width, hr = lrn * s * s;
+    const bool net = y_out || rgb_out, luma = net || y_bicubic, colour = rgb_bicubic || rgb_out;
+    // col_rgb: upscaled RGB | input RGB, as dcscn_sr_rgb lays them out; col_d2: the uint8 results y_bicubic | y_out | rgb_out
+    const size_t plane = (hr + 15) & ~(size_t)15;
+    int rc = ensure_io(h, lrn, hr);
+    if (!rc) rc = grow(h, &h->col_rgb, &h->col_rgb_cap, (3 * hr + 3) / 4 + (3 * lrn + 3) / 4 + 4, h->stream);
+    if (!rc) rc = grow(h, &h->col_d2, &h->col_d2_cap, (2 * plane + 3 * hr + 3) / 4, h->stream);
+    if (rc) return rc;
+    uint8_t* d_up = reinterpret_cast<uint8_t*>(h->col_rgb);
+    uint8_t* d_lr = d_up + ((3 * hr + 15) & ~(size_t)15);
+    uint8_t* d_yb = reinterpret_cast<uint8_t*>(h->col_d2);
+    uint8_t *d_yo = d_yb + plane, *d_ro = d_yo + plane;
+    HIP_TRY(h, hipMemcpy(d_lr, rgb, 3 * lrn, hipMemcpyHostToDevice));
+    // resize_image_by_pil(org_image, scale): the "_bicubic" file and the CbCr of the result (DCSCN.py:594, 603)
+    if (colour && (rc = resize_device_bytes(h, d_lr, d_up, 1, height, width, 3, height * s, width * s, h->stream))) return rc;
+    if (luma) {
+        // input_y_image = convert_rgb_to_y(org_image); x = float32(Y), x2 = its BICUBIC (DCSCN.py:597-601, 552-554)
+        HIP_TRY(h, rgb_to_y_launch(d_lr, nullptr, h->io_x, (long long)lrn, h->stream));
+        rc = net ? sr_from_lr_on_device(h, height, width, n_ensemble)
+                 : resize_device(h, h->io_x, h->io_x2, 1, height, width, height * s, width * s, h->stream);
+        if (rc) return rc;
+    }
+    const double* y64 = n_ensemble > 1 ? reinterpret_cast<const double*>(h->ens_out) : nullptr;
+    const float* y32 = n_ensemble > 1 ? nullptr : h->io_y;
+    if (y_bicubic) HIP_TRY(h, cast_bytes_launch(nullptr, h->io_x2, d_yb, (long long)hr, h->stream));
+    if (y_out) HIP_TRY(h, cast_bytes_launch(y64, y32, d_yo, (long long)hr, h->stream));
+    if (rgb_out) HIP_TRY(h, y_cbcr_to_rgb_bytes_launch(y64, y32, d_up, d_ro, (long long)hr, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (rgb_bicubic) HIP_TRY(h, hipMemcpy(rgb_bicubic, d_up, 3 * hr, hipMemcpyDeviceToHost));
+    if (y_bicubic) HIP_TRY(h, hipMemcpy(y_bicubic, d_yb, hr, hipMemcpyDeviceToHost));
+    if (y_out) HIP_TRY(h, hipMemcpy(y_out, d_yo, hr, hipMemcpyDeviceToHost));
+    if (rgb_out) HIP_TRY(h, hipMemcpy(rgb_out, d_ro, 3 * hr, hipMemcpyDeviceToHost));
     return DCSCN_OK;
 }
 

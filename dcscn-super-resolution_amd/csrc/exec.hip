@@ -765,4 +765,45 @@ int resize_device(dcscn_ctx* h, const float* in, float* out, int n, int H, int W
     return DCSCN_OK;
 }
 
+// the (in, out) table of resample_table with its 8-bpc weights (resample_coeffs8), made on first use
+static int resample_table8(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::ResampleTable** out) {
+    const dcscn_ctx::ResampleTable* t;
+    int rc = resample_table(h, in_size, out_size, &t);
+    if (rc) return rc;
+    dcscn_ctx::ResampleTable& e = h->resample_tables[std::make_pair(in_size, out_size)];
+    if (!e.d_k8) {
+        std::vector<int> bounds, k8;
+        resample_coeffs8(in_size, out_size, &bounds, &k8);
+        if ((rc = upload_vec(h, k8, &e.d_k8))) return rc;
+    }
+    *out = &e;
+    return DCSCN_OK;
+}
+
+// Pillow's mode "L" (C = 1) / "RGB" (C = 3, interleaved) resize of n uint8 images [H, W, C] -> [OH, OW, C], device pointers:
+// horizontal pass into a uint8 intermediate (rs_tmp), then the vertical pass; a pass whose size does not change is skipped
+int resize_device_bytes(dcscn_ctx* h, const uint8_t* in, uint8_t* out, int n, int H, int W, int C, int OH, int OW, hipStream_t stream) {
+    if (n <= 0) return DCSCN_OK;
+    const uint8_t* src = in;
+    const dcscn_ctx::ResampleTable* t;
+    int rc;
+    if (OW != W) {
+        if ((rc = resample_table8(h, W, OW, &t))) return rc;
+        uint8_t* dst = out;
+        if (OH != H) {
+            if ((rc = grow(h, &h->rs_tmp, &h->rs_tmp_cap, ((size_t)n * H * OW * C + 3) / 4, stream))) return rc;
+            dst = reinterpret_cast<uint8_t*>(h->rs_tmp);
+        }
+        HIP_TRY(h, resample_h8_launch(src, dst, t->d_bounds, t->d_k8, t->ksize, (long long)n * H, W, OW, C, stream));
+        src = dst;
+    }
+    if (OH != H) {
+        if ((rc = resample_table8(h, H, OH, &t))) return rc;
+        HIP_TRY(h, resample_v8_launch(src, out, t->d_bounds, t->d_k8, t->ksize, n, H, OH, OW * C, stream));
+    } else if (OW == W) {
+        HIP_TRY(h, hipMemcpyAsync(out, in, (size_t)n * H * W * C, hipMemcpyDeviceToDevice, stream));
+    }
+    return DCSCN_OK;
+}
+
 }  // namespace dcscn_impl

@@ -311,6 +311,9 @@ hipError_t rgb_to_y_launch(const uint8_t* rgb, double* y64, float* y32, long lon
 hipError_t rgb_to_ycbcr_launch(const uint8_t* rgb, double* out, long long n, hipStream_t stream);
 hipError_t y_cbcr_to_rgb_launch(const double* y64, const float* y32, const double* cbcr, const uint8_t* rgb8, double* out, long long n,
                                 hipStream_t stream);
+// the same RGB (CbCr from rgb8) / a single-channel float32 or float64 image, cast to uint8 as save_image casts (truncate, low 8 bits)
+hipError_t y_cbcr_to_rgb_bytes_launch(const double* y64, const float* y32, const uint8_t* rgb8, uint8_t* out, long long n, hipStream_t stream);
+hipError_t cast_bytes_launch(const double* v64, const float* v32, uint8_t* out, long long n, hipStream_t stream);
 
 // PSNR / SSIM of two single-channel images (metrics.hip): trimmed like a saved file, shaved by `border`; h, w = the shaved size
 // (h >= kMetricTaps, w >= 1), stride = the row length of both images; each image is float64 or, with its *32 pointer set, float32.
@@ -327,6 +330,13 @@ hipError_t resample_h_launch(const float* in, float* out, const int* bounds, con
                              long long rows, int w, int ow, hipStream_t stream);
 hipError_t resample_v_launch(const float* in, float* out, const int* bounds, const double* kk, int ksize,
                              int n_img, int h, int oh, int w, hipStream_t stream);
+// ... and of uint8 images with c interleaved channels (Pillow's 8-bpc path: modes "L" / "RGB"): k8 = the weights as int32 with 22
+// fraction bits; rows of w * c (h pass) / wc (v pass) bytes, any alignment of `out`
+int resample_coeffs8(int in_size, int out_size, std::vector<int>* bounds, std::vector<int>* k8);     // returns ksize
+hipError_t resample_h8_launch(const uint8_t* in, uint8_t* out, const int* bounds, const int* k8, int ksize, long long rows, int w, int ow,
+                              int c, hipStream_t stream);
+hipError_t resample_v8_launch(const uint8_t* in, uint8_t* out, const int* bounds, const int* k8, int ksize, int n_img, int h, int oh,
+                              int wc, hipStream_t stream);
 // widest channel tile (units of 16) of the conv_igemm<ks, ...> family
 int conv_max_nt(int ks);
 // LDS bytes of conv_cin1 / conv_cout1 for a kernel size (both must fit 64 KB)

@@ -179,7 +179,7 @@ struct dcscn_ctx {
     float* io_x = nullptr; float* io_x2 = nullptr; float* io_y = nullptr;
     size_t io_x_cap = 0, io_x2_cap = 0, io_y_cap = 0;
     // bicubic resize (resample.hip): Pillow coefficient tables per (in, out) size, and the intermediate image; d_k8 = the
-    // 8-bit fixed-point form of d_kk (train_data.hip, made on first use)
+    // 8-bit fixed-point form of d_kk (resize_device_bytes, made on first use)
     struct ResampleTable { int ksize = 0; int* d_bounds = nullptr; double* d_kk = nullptr; int* d_k8 = nullptr; };
     std::map<std::pair<int, int>, ResampleTable> resample_tables;
     float* rs_tmp = nullptr; size_t rs_tmp_cap = 0;
@@ -341,5 +341,7 @@ int grow(dcscn_ctx* h, T** p, size_t* cap, size_t count, hipStream_t stream, int
     return DCSCN_OK;
 }
 int resize_device(dcscn_ctx* h, const float* in, float* out, int n, int H, int W, int OH, int OW, hipStream_t stream);
+// the same for uint8 images of C = 1 or 3 interleaved channels (Pillow's modes "L" / "RGB")
+int resize_device_bytes(dcscn_ctx* h, const uint8_t* in, uint8_t* out, int n, int H, int W, int C, int OH, int OW, hipStream_t stream);
 
 }  // namespace dcscn_impl

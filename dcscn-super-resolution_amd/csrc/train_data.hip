@@ -7,7 +7,7 @@
 //   batch_gather  (1 launch per 32 patches)  crop + Y / grey + fliplr into compact HR planes (float32 for RGB patches, uint8
 //                                            for grey ones, numbered in batch order per kind); writes y_true
 //   resize_device (4 launches, RGB patches)  resample.hip's mode-"F" kernels: HR -> LR -> x2
-//   resample_*8   (4 launches, grey patches) Pillow's 8-bpc kernels: HR -> LR -> x2 through uint8 intermediates
+//   resize_device_bytes (4 launches, grey patches) resample.hip's 8-bpc kernels: HR -> LR -> x2 through uint8 intermediates
 //   batch_finish  (1 launch per 32 patches)  max_value and float32 cast of LR and x2 into x, x2
 // Everything here is a few hundred KB of elementwise work per batch; the kernels are the plain one-thread-per-pixel form.
 #include "plan.h"
@@ -30,7 +30,6 @@ struct TrainBatches {
 namespace {
 
 constexpr int kChunk = 32;          // patches per gather / finish launch (their descriptors travel as kernel arguments)
-constexpr int kPrecisionBits = 22;  // Pillow Resample.c: PRECISION_BITS = 32 - 8 - 2
 
 struct PatchDesc {
     const uint8_t* px;              // the image, [H, W, c] uint8
@@ -68,43 +67,6 @@ __global__ __launch_bounds__(256) void batch_gather_kernel(PatchChunk pc, int hr
     y_true[(size_t)blockIdx.y * hr2 + idx] = (float)(mul ? v * scale : v);
 }
 
-// Pillow ImagingResampleHorizontal_8bpc: out[row][xx] = clip8((1 << 21 + sum_i in[row][xmin + i] * k8[xx][i]) >> 22)
-__device__ __forceinline__ uint8_t clip8(int ss) {
-    const int v = ss >> kPrecisionBits;
-    return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
-}
-
-__global__ __launch_bounds__(256) void resample_h8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
-                                                          const int* __restrict__ kk, int ksize, long long rows, int w, int ow) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * ow) return;
-    const int xx = (int)(idx % ow);
-    const long long row = idx / ow;
-    const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
-    const uint8_t* p = in + row * w + xmin;
-    const int* k = kk + (size_t)xx * ksize;
-    int ss = 1 << (kPrecisionBits - 1);
-    for (int i = 0; i < n; ++i) ss += (int)p[i] * k[i];
-    out[idx] = clip8(ss);
-}
-
-// ImagingResampleVertical_8bpc
-__global__ __launch_bounds__(256) void resample_v8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
-                                                          const int* __restrict__ kk, int ksize, int n_img, int h, int oh, int w) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n_img * oh * w) return;
-    const int x = (int)(idx % w);
-    const long long t = idx / w;
-    const int yy = (int)(t % oh);
-    const long long img = t / oh;
-    const int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
-    const uint8_t* p = in + (img * h + ymin) * w + x;
-    const int* k = kk + (size_t)yy * ksize;
-    int ss = 1 << (kPrecisionBits - 1);
-    for (int i = 0; i < n; ++i) ss += (int)p[(size_t)i * w] * k[i];
-    out[idx] = clip8(ss);
-}
-
 // load_batch_image's max_value rule and train_batch's float32 cast: float32 planes (RGB) times float32(scale); uint8 planes
 // (grey) times scale in float64 (numpy: uint8 array * Python float -> float64)
 __device__ __forceinline__ float cast_rgb(float v, int mul, double scale) { return mul ? v * (float)scale : v; }
@@ -124,50 +86,6 @@ __global__ __launch_bounds__(256) void batch_finish_kernel(PatchChunk pc, int lr
 }
 
 static unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
-
-// the (in, out) table of resample_table with its 8-bpc form (Resample.c normalize_coeffs_8bpc), made on first use
-int resample_table8(dcscn_ctx* h, int in_size, int out_size, const dcscn_ctx::ResampleTable** out) {
-    const dcscn_ctx::ResampleTable* t;
-    int rc = resample_table(h, in_size, out_size, &t);
-    if (rc) return rc;
-    dcscn_ctx::ResampleTable& e = h->resample_tables[std::make_pair(in_size, out_size)];
-    if (!e.d_k8) {
-        std::vector<int> bounds;
-        std::vector<double> kk;
-        resample_coeffs(in_size, out_size, &bounds, &kk);
-        std::vector<int> k8(kk.size());
-        for (size_t i = 0; i < kk.size(); ++i)
-            k8[i] = kk[i] < 0 ? (int)(-0.5 + kk[i] * (1 << kPrecisionBits)) : (int)(0.5 + kk[i] * (1 << kPrecisionBits));
-        if ((rc = upload_vec(h, k8, &e.d_k8))) return rc;
-    }
-    *out = &e;
-    return DCSCN_OK;
-}
-
-// Pillow mode "L" resize of n uint8 images [H, W] -> [OH, OW]: horizontal pass into tmp [n, H, OW], then the vertical pass
-// (a pass whose size does not change is skipped, as resize_device does)
-int resize_device8(dcscn_ctx* h, const uint8_t* in, uint8_t* tmp, uint8_t* out, int n, int H, int W, int OH, int OW, hipStream_t st) {
-    if (n <= 0) return DCSCN_OK;
-    const uint8_t* src = in;
-    const dcscn_ctx::ResampleTable* t;
-    int rc;
-    if (OW != W) {
-        if ((rc = resample_table8(h, W, OW, &t))) return rc;
-        uint8_t* dst = OH != H ? tmp : out;
-        const long long rows = (long long)n * H;
-        hipLaunchKernelGGL(resample_h8_kernel, dim3(blocks(rows * OW)), dim3(256), 0, st, src, dst, t->d_bounds, t->d_k8, t->ksize, rows, W, OW);
-        HIP_TRY(h, hipGetLastError());
-        src = dst;
-    }
-    if (OH != H) {
-        if ((rc = resample_table8(h, H, OH, &t))) return rc;
-        hipLaunchKernelGGL(resample_v8_kernel, dim3(blocks((long long)n * OH * OW)), dim3(256), 0, st, src, out, t->d_bounds, t->d_k8, t->ksize, n, H, OH, OW);
-        HIP_TRY(h, hipGetLastError());
-    } else if (OW == W) {
-        HIP_TRY(h, hipMemcpyAsync(out, in, (size_t)n * H * W, hipMemcpyDeviceToDevice, st));
-    }
-    return DCSCN_OK;
-}
 
 inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
@@ -199,16 +117,16 @@ int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int L, double 
     const size_t hr2 = (size_t)HR * HR, lr2 = (size_t)L * L;
     int n_f = 0, n_g = 0;
     for (int i = 0; i < n; ++i) (b->images[p[i].image].C == 1 ? n_g : n_f) += 1;
-    // planes: float32 HR, LR, x2 of the RGB patches, then uint8 HR, h-pass rows, LR, x2 of the grey ones
-    size_t off[7], bytes = 0;
-    const size_t sizes[7] = {(size_t)n_f * hr2 * 4, (size_t)n_f * lr2 * 4, (size_t)n_f * hr2 * 4, (size_t)n_g * hr2, (size_t)n_g * HR * L,
-                             (size_t)n_g * lr2, (size_t)n_g * hr2};
-    for (int k = 0; k < 7; ++k) { off[k] = bytes; bytes += align256(sizes[k]); }
+    // planes: float32 HR, LR, x2 of the RGB patches, then uint8 HR, LR, x2 of the grey ones
+    size_t off[6], bytes = 0;
+    const size_t sizes[6] = {(size_t)n_f * hr2 * 4, (size_t)n_f * lr2 * 4, (size_t)n_f * hr2 * 4, (size_t)n_g * hr2, (size_t)n_g * lr2,
+                             (size_t)n_g * hr2};
+    for (int k = 0; k < 6; ++k) { off[k] = bytes; bytes += align256(sizes[k]); }
     int rc = grow(h, &b->planes, &b->planes_cap, bytes / 4, st);
     if (rc) return rc;
     char* base = reinterpret_cast<char*>(b->planes);
     float *f_hr = (float*)(base + off[0]), *f_lr = (float*)(base + off[1]), *f_x2 = (float*)(base + off[2]);
-    uint8_t *g_hr = (uint8_t*)(base + off[3]), *g_tmp = (uint8_t*)(base + off[4]), *g_lr = (uint8_t*)(base + off[5]), *g_x2 = (uint8_t*)(base + off[6]);
+    uint8_t *g_hr = (uint8_t*)(base + off[3]), *g_lr = (uint8_t*)(base + off[4]), *g_x2 = (uint8_t*)(base + off[5]);
     // ordered behind a forward / resize of this handle on another stream (resize_device's row buffer rs_tmp is shared)
     if (h->has_last && h->last_stream != st) HIP_TRY(h, hipStreamWaitEvent(st, h->done_ev, 0));
 
@@ -227,8 +145,8 @@ int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int L, double 
     }
     if ((rc = resize_device(h, f_hr, f_lr, n_f, HR, HR, L, L, st))) return rc;
     if ((rc = resize_device(h, f_lr, f_x2, n_f, L, L, HR, HR, st))) return rc;
-    if ((rc = resize_device8(h, g_hr, g_tmp, g_lr, n_g, HR, HR, L, L, st))) return rc;
-    if ((rc = resize_device8(h, g_lr, g_tmp, g_x2, n_g, L, L, HR, HR, st))) return rc;
+    if ((rc = resize_device_bytes(h, g_hr, g_lr, n_g, HR, HR, 1, L, L, st))) return rc;
+    if ((rc = resize_device_bytes(h, g_lr, g_x2, n_g, L, L, 1, HR, HR, st))) return rc;
     for (size_t c = 0; c < chunks.size(); ++c) {
         const int cnt = std::min(kChunk, n - (int)c * kChunk);
         hipLaunchKernelGGL(batch_finish_kernel, dim3(blocks((long long)hr2), cnt), dim3(256), 0, st, chunks[c], L, HR, mul, scale, f_lr, f_x2,

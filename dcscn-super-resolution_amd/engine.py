@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "dcscn_psnr_ssim", "dcscn_evaluate_rgb_metrics",
     "dcscn_train_record_floats", "dcscn_train_local_gradients_device", "dcscn_train_local_gradients_patches",
     "dcscn_train_apply_records",
+    "dcscn_resample_table_bytes", "dcscn_resize_bicubic_bytes", "dcscn_resize_bicubic_bytes_device", "dcscn_sr_rgb_bytes",
 )
 
 # dcscn_optimizer; the names of helper/args.py --optimizer
@@ -184,6 +185,10 @@ def load_library():
     lib.dcscn_convert_y_and_cbcr_to_rgb.argtypes = [vp, dp, dp, dp, c.c_int64]
     lib.dcscn_evaluate_rgb.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, dp, fp, dp]
     lib.dcscn_sr_rgb.argtypes = [vp, u8p, u8p, c.c_int, c.c_int, c.c_int, dp, dp]
+    lib.dcscn_resample_table_bytes.argtypes = [c.c_int, c.c_int, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int32), c.c_int]
+    lib.dcscn_resize_bicubic_bytes.argtypes = [vp, u8p, u8p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int]
+    lib.dcscn_resize_bicubic_bytes_device.argtypes = [vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, vp]
+    lib.dcscn_sr_rgb_bytes.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, u8p, u8p, u8p, u8p]
     lib.dcscn_psnr_ssim.argtypes = [vp, dp, dp, c.c_int, c.c_int, c.c_int, c.POINTER(Metrics)]
     lib.dcscn_evaluate_rgb_metrics.argtypes = [vp, u8p, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(Metrics), c.POINTER(Metrics), dp]
     lib.dcscn_synchronize.argtypes = [vp]
@@ -289,6 +294,24 @@ def resample_table(in_size, out_size):
     if rc:
         raise EngineError(rc, "dcscn_resample_table(%d, %d)" % (in_size, out_size))
     return bounds, weights
+
+
+def resample_table_bytes(in_size, out_size):
+    """(bounds [out, 2] int32, coeffs [out, ksize] int32) of the Pillow-compatible 8-bit bicubic resize along one axis: the
+    weights of resample_table with 22 fraction bits (dcscn_resample_table_bytes); host code of the library, needs no GPU."""
+    lib = load_library()
+    ks = ctypes.c_int(0)
+    rc = lib.dcscn_resample_table_bytes(int(in_size), int(out_size), ctypes.byref(ks), None, None, 0)
+    if rc:
+        raise EngineError(rc, "dcscn_resample_table_bytes(%d, %d)" % (in_size, out_size))
+    bounds = np.zeros((int(out_size), 2), np.int32)
+    coeffs = np.zeros((int(out_size), ks.value), np.int32)
+    rc = lib.dcscn_resample_table_bytes(int(in_size), int(out_size), ctypes.byref(ks),
+                                        bounds.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                        coeffs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), coeffs.size)
+    if rc:
+        raise EngineError(rc, "dcscn_resample_table_bytes(%d, %d)" % (in_size, out_size))
+    return bounds, coeffs
 
 
 class Engine:
@@ -451,6 +474,26 @@ class Engine:
         self._check(self._lib.dcscn_resize_bicubic(self._h, a.ctypes.data_as(fp), out.ctypes.data_as(fp), n, h, w,
                                                    int(out_height), int(out_width)))
         return out[0] if single else out
+
+    def resize_bicubic_bytes(self, images, out_height, out_width):
+        """Pillow's Image.resize(BICUBIC) of uint8 images on the device, bit-identical: [h, w] (mode 'L'), [h, w, 3] ('RGB') or a
+        batch [n, h, w, 1 | 3] -> the same layout at [out_height, out_width]."""
+        a = np.ascontiguousarray(images)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
+            raise EngineError(1, "expected uint8 images [h, w], [h, w, 3] or [n, h, w, c], got %s %s" % (a.dtype, a.shape))
+        n, h, w = (1,) + a.shape[:2] if a.ndim < 4 else a.shape[:3]
+        ch = 1 if a.ndim == 2 else a.shape[-1]
+        oh, ow = int(out_height), int(out_width)
+        out = np.empty((oh, ow) if a.ndim == 2 else a.shape[:-3] + (oh, ow, ch), np.uint8)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.dcscn_resize_bicubic_bytes(self._h, a.ctypes.data_as(u8), out.ctypes.data_as(u8), n, h, w, ch, oh, ow))
+        return out
+
+    def resize_bicubic_bytes_device(self, in_ptr, out_ptr, n, h, w, channels, out_height, out_width, stream=None):
+        """resize_bicubic_bytes on device pointers (ints), enqueued on ``stream`` (None / 0: the handle's own); does not synchronise."""
+        self._check(self._lib.dcscn_resize_bicubic_bytes_device(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), int(n), int(h), int(w),
+                                                                int(channels), int(out_height), int(out_width),
+                                                                ctypes.c_void_p(stream) if stream else None))
 
     def stream(self):
         """The handle's own hipStream_t as an int (non-blocking: not ordered against the legacy default stream)."""
@@ -711,6 +754,24 @@ class Engine:
         if n_ensemble <= 1:
             y = y.astype(np.float32)
         return y, rgb
+
+    SR_BYTES_OUTPUTS = ("rgb_bicubic", "y_bicubic", "y_out", "rgb_out")
+
+    def sr_rgb_bytes(self, image, n_ensemble=1, want=SR_BYTES_OUTPUTS):
+        """do_for_file's colour branch from one upload of the uint8 RGB ``image``, every result as the uint8 array save_image
+        would write: {"rgb_bicubic": [s*h, s*w, 3], "y_bicubic": [s*h, s*w, 1], "y_out": [s*h, s*w, 1], "rgb_out": [s*h, s*w, 3]},
+        restricted to the names in ``want`` (dcscn_sr_rgb_bytes)."""
+        a = self._rgb8(image)
+        h, w = a.shape[:2]
+        s = self.scale
+        unknown = [k for k in want if k not in self.SR_BYTES_OUTPUTS]
+        if unknown or not want:
+            raise EngineError(1, "want must name some of %s, got %s" % (self.SR_BYTES_OUTPUTS, tuple(want)))
+        out = {k: np.empty((h * s, w * s, 3 if k.startswith("rgb") else 1), np.uint8) for k in self.SR_BYTES_OUTPUTS if k in want}
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        ptrs = [out[k].ctypes.data_as(u8) if k in out else None for k in self.SR_BYTES_OUTPUTS]
+        self._check(self._lib.dcscn_sr_rgb_bytes(self._h, a.ctypes.data_as(u8), h, w, max(1, int(n_ensemble)), *ptrs))
+        return out
 
     def forward_ensemble(self, x, x2, n_ensemble):
         """One image [h, w(,1)] + bicubic [s*h, s*w(,1)] -> float64 [s*h, s*w, 1] (do(), DCSCN.py:559-573)."""

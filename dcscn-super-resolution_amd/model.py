@@ -584,8 +584,8 @@ class SuperResolution:
         ch = input_image.shape[2] if len(input_image.shape) > 2 else 1
         if ch != 1:
             raise ValueError("do() expects a single-channel image, got %d channels" % ch)
-        # the device bicubic reproduces Pillow's mode-'F' path (float images).  A uint8 single-channel image goes through
-        # Pillow's mode 'L' in the reference (utilty.py:229-232: rounded and clipped to 0..255), so it stays on the host
+        # the device bicubic reproduces Pillow's mode-'F' path (float images) here.  A uint8 single-channel image goes through
+        # Pillow's mode 'L' in the reference (utilty.py:229-232: rounded and clipped to 0..255): _resize_bytes below
         if bicubic_input_image is None and self.resampling_method == "bicubic" and np.issubdtype(np.asarray(input_image).dtype, np.floating):
             # DCSCN.py:552-554 on the device: dcscn_resize_bicubic is bit-compatible with Pillow's mode-'F' BICUBIC
             # (tests/test_resize_hip.py), so x2 never has to be built or uploaded by the host
@@ -595,8 +595,7 @@ class SuperResolution:
                 return eng.forward_lr(x[None])[0]
             bicubic_input_image = eng.resize_bicubic(x, self.scale * h, self.scale * w).reshape(self.scale * h, self.scale * w, 1)
         elif bicubic_input_image is None:
-            bicubic_input_image = util.resize_image_by_pil(input_image, self.scale,
-                                                           resampling_method=self.resampling_method)
+            bicubic_input_image = self._resize_bytes(input_image, self.scale)
         if self.max_value != 255.0:
             input_image = np.multiply(input_image, self.max_value / 255.0)
             bicubic_input_image = np.multiply(bicubic_input_image, self.max_value / 255.0)
@@ -631,29 +630,48 @@ class SuperResolution:
         output_folder += "/" + self.name + "/"
         util.save_image(output_folder + filename + extension, org_image)
 
-        scaled_image = util.resize_image_by_pil(org_image, self.scale, resampling_method=self.resampling_method)
-        util.save_image(output_folder + filename + "_bicubic" + extension, scaled_image)
-
-        if len(org_image.shape) >= 3 and org_image.shape[2] == 3 and self.channels == 1:
+        colour = len(org_image.shape) >= 3 and org_image.shape[2] == 3 and self.channels == 1
+        if colour and self._device_colour_path(org_image):
+            # both bicubic images, Y, the forward pass, the YCbCr -> RGB recombination and save_image's uint8 cast in one
+            # device pipeline from one upload (dcscn_sr_rgb_bytes): the four arrays arrive as the bytes of their files
+            out = self._ready_engine().sr_rgb_bytes(org_image, self.self_ensemble)
+            util.save_image(output_folder + filename + "_bicubic" + extension, out["rgb_bicubic"])
+            util.save_image(output_folder + filename + "_bicubic_y" + extension, out["y_bicubic"])
+            util.save_image(output_folder + filename + "_result_y" + extension, out["y_out"])
+            util.save_image(output_folder + filename + "_result" + extension, out["rgb_out"])
+            return
+        if colour:
+            scaled_image = util.resize_image_by_pil(org_image, self.scale, resampling_method=self.resampling_method)
+            util.save_image(output_folder + filename + "_bicubic" + extension, scaled_image)
             input_y_image = util.convert_rgb_to_y(org_image)
             scaled_image = util.resize_image_by_pil(input_y_image, self.scale, resampling_method=self.resampling_method)
             util.save_image(output_folder + filename + "_bicubic_y" + extension, scaled_image)
-            if self._device_colour_path(org_image):
-                # Y, x2, the forward pass and the YCbCr -> RGB recombination in one device pipeline (dcscn_sr_rgb)
-                scaled_rgb = util.resize_image_by_pil(org_image, self.scale, self.resampling_method)
-                output_y_image, image = self._ready_engine().sr_rgb(org_image, scaled_rgb, self.self_ensemble)
-                util.save_image(output_folder + filename + "_result_y" + extension, output_y_image)
-            else:
-                output_y_image = self.do(input_y_image)
-                util.save_image(output_folder + filename + "_result_y" + extension, output_y_image)
-                scaled_ycbcr_image = util.convert_rgb_to_ycbcr(
-                    util.resize_image_by_pil(org_image, self.scale, self.resampling_method))
-                image = util.convert_y_and_cbcr_to_rgb(output_y_image, scaled_ycbcr_image[:, :, 1:3])
+            output_y_image = self.do(input_y_image)
+            util.save_image(output_folder + filename + "_result_y" + extension, output_y_image)
+            scaled_ycbcr_image = util.convert_rgb_to_ycbcr(
+                util.resize_image_by_pil(org_image, self.scale, self.resampling_method))
+            image = util.convert_y_and_cbcr_to_rgb(output_y_image, scaled_ycbcr_image[:, :, 1:3])
         else:
-            scaled_image = util.resize_image_by_pil(org_image, self.scale, resampling_method=self.resampling_method)
+            scaled_image = self._resize_bytes(org_image, self.scale)      # (the reference resizes twice: one image, two files)
+            util.save_image(output_folder + filename + "_bicubic" + extension, scaled_image)
             util.save_image(output_folder + filename + "_bicubic_y" + extension, scaled_image)
             image = self.do(org_image)
         util.save_image(output_folder + filename + "_result" + extension, image)
+
+    def _device_byte_resize(self, image):
+        """A uint8 image of 1 or 3 channels through the device's 8-bit bicubic (Pillow's modes 'L' / 'RGB', bit-identical); it
+        needs an engine but no weights.  Other resampling methods stay with Pillow."""
+        return (self.resampling_method == BICUBIC_METHOD_STRING and self._engine is not None and image.dtype == np.uint8
+                and (image.ndim == 2 or (image.ndim == 3 and image.shape[2] in (1, 3))))
+
+    def _resize_bytes(self, image, scale):
+        """util.resize_image_by_pil(image, scale, self.resampling_method), on the device where _device_byte_resize allows."""
+        image = np.asarray(image)
+        if not self._device_byte_resize(image):
+            return util.resize_image_by_pil(image, scale, resampling_method=self.resampling_method)
+        height, width = image.shape[0], image.shape[1]
+        out = self._engine.resize_bicubic_bytes(image, int(height * scale), int(width * scale))
+        return out.reshape(out.shape[0], out.shape[1], -1)
 
     def _device_colour_path(self, image):
         """uint8 RGB through the device colour / bicubic kernels: they reproduce the float64 numpy colour math and
@@ -695,7 +713,7 @@ class SuperResolution:
             true_y = true_image
         else:
             return true_image, None, None, None
-        bicubic = util.resize_image_by_pil(input_image, self.scale, resampling_method=self.resampling_method)
+        bicubic = self._resize_bytes(input_image, self.scale)              # uint8 for grey files; the float Y goes through Pillow
         return true_image, true_y, input_image, bicubic
 
     def do_for_evaluate(self, file_path, print_console=False):
@@ -783,8 +801,8 @@ class SuperResolution:
         util.make_dir(output_directory)
 
         true_image = util.set_image_alignment(util.load_image(file_path, print_console=False), self.scale)
-        input_image = util.resize_image_by_pil(true_image, 1.0 / self.scale, resampling_method=self.resampling_method)
-        input_bicubic_image = util.resize_image_by_pil(input_image, self.scale, resampling_method=self.resampling_method)
+        input_image = self._resize_bytes(true_image, 1.0 / self.scale)
+        input_bicubic_image = self._resize_bytes(input_image, self.scale)
         util.save_image(output_directory + filename + "_input_bicubic" + extension, input_bicubic_image)
 
         if true_image.shape[2] == 3 and self.channels == 1:
@@ -807,8 +825,7 @@ class SuperResolution:
             util.save_image(output_directory + filename + "_loss" + extension, loss_image)
         elif true_image.shape[2] == 1 and self.channels == 1:
             input_image = build_input_image(true_image, channels=self.channels, scale=self.scale, alignment=self.scale)
-            input_bicubic_y_image = util.resize_image_by_pil(input_image, self.scale,
-                                                             resampling_method=self.resampling_method)
+            input_bicubic_y_image = self._resize_bytes(input_image, self.scale)
             output_image = self.do(input_image, input_bicubic_y_image)
             psnr, ssim = self._metrics(true_image, output_image)
             util.save_image(output_directory + file_path, true_image)

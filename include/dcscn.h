@@ -289,6 +289,20 @@ int dcscn_resample_table(int in_size, int out_size, int* ksize, int* bounds, dou
 int dcscn_resize_bicubic_device(dcscn_handle h, const float* in, float* out, int n, int height, int width,
                                 int out_height, int out_width, void* stream);
 
+/* The 8-bit form of dcscn_resample_table (Pillow's normalize_coeffs_8bpc: the weights as int32 with 22 fraction bits,
+ * rounded half away from zero): bounds as there, `coeffs[i * ksize + t]`.  Host only, needs no device; NULL tables query
+ * `ksize`; `capacity` is the number of int32 values `coeffs` can hold. */
+int dcscn_resample_table_bytes(int in_size, int out_size, int* ksize, int* bounds, int32_t* coeffs, int capacity);
+/* Image.resize(BICUBIC) of `n` uint8 images of mode "L" (channels = 1) or "RGB" (channels = 3, interleaved), bit-identical
+ * to Pillow (int32 fixed point, horizontal pass into a uint8 intermediate, then the vertical pass): replaces
+ * util.resize_image_by_pil for the 8-bit images of sr.py / evaluate.py.  Host buffers, synchronous; the _device form takes
+ * device pointers of any alignment and a hipStream_t (NULL = the handle's stream) and does not synchronise.  Usable before
+ * dcscn_finalize.  Other channel counts: DCSCN_ERR_INVALID_ARG. */
+int dcscn_resize_bicubic_bytes(dcscn_handle h, const uint8_t* in, uint8_t* out, int n, int height, int width, int channels,
+                               int out_height, int out_width);
+int dcscn_resize_bicubic_bytes_device(dcscn_handle h, const uint8_t* in, uint8_t* out, int n, int height, int width, int channels,
+                                      int out_height, int out_width, void* stream);
+
 /* do(input_image, bicubic_input_image=None) (DCSCN.py:547-554): x2 is the bicubic upscale of x, computed on the
  * device with dcscn_resize_bicubic; otherwise as dcscn_forward. */
 int dcscn_forward_lr(dcscn_handle h, const float* x, float* y, int n, int height, int width);
@@ -358,12 +372,23 @@ int dcscn_evaluate_rgb_metrics(dcscn_handle h, const uint8_t* rgb, int height, i
                                dcscn_metrics* model, dcscn_metrics* bicubic, double* y);
 
 /* do_for_file's colour pipeline (sr.py; DCSCN.py:588-614): rgb uint8 [height, width, 3] is the input image,
- * rgb_upscaled uint8 [s*height, s*width, 3] its Pillow-upscaled copy (the reference builds it on the host for the
- * "_bicubic" output anyway; Pillow's uint8 RGB resize is integer arithmetic and stays there).  Device: Y of the input
+ * rgb_upscaled uint8 [s*height, s*width, 3] its Pillow-upscaled copy (built by the caller, on the host or with
+ * dcscn_resize_bicubic_bytes; dcscn_sr_rgb_bytes below builds it on the device itself).  Device: Y of the input
  * -> x, x2 = BICUBIC(x), do() -> y; CbCr of rgb_upscaled; rgb_out = convert_y_and_cbcr_to_rgb(y, cbcr), float64
  * [s*height, s*width, 3].  y (optional) receives the super-resolved luma, float64. */
 int dcscn_sr_rgb(dcscn_handle h, const uint8_t* rgb, const uint8_t* rgb_upscaled, int height, int width, int n_ensemble,
                  double* y, double* rgb_out);
+
+/* The same pipeline from ONE upload of the uint8 RGB input, every result as the bytes save_image would write (its cast is
+ * numpy's astype(uint8): truncate toward zero to a 32-bit integer, keep the low 8 bits -- values outside 0..255 wrap).
+ * Each output is optional (at least one non-null), uint8, of the upscaled size sh = s*height, sw = s*width:
+ *   rgb_bicubic [sh, sw, 3]  resize_image_by_pil(rgb, s)                                      ("_bicubic")
+ *   y_bicubic   [sh, sw]     cast(BICUBIC of float32(Y)) -- the x2 the forward consumes       ("_bicubic_y")
+ *   y_out       [sh, sw]     cast(do(Y))                                                      ("_result_y")
+ *   rgb_out     [sh, sw, 3]  cast(convert_y_and_cbcr_to_rgb(do(Y), CbCr of rgb_bicubic))      ("_result")
+ * The network runs only when y_out or rgb_out is asked for. */
+int dcscn_sr_rgb_bytes(dcscn_handle h, const uint8_t* rgb, int height, int width, int n_ensemble, uint8_t* rgb_bicubic,
+                       uint8_t* y_bicubic, uint8_t* y_out, uint8_t* rgb_out);
 
 /* Per-launch (dcscn_op_info order) device milliseconds, summed over sub-batches and averaged over
  * the forwards run with the profile option on since the previous call (which this call resets);
