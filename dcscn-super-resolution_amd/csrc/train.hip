@@ -45,12 +45,15 @@ __device__ inline float tact(float z, float alpha, int act) {
         default:          return z;
     }
 }
-__device__ inline float tact_grad(float z, float alpha, int act) {
+// At z == 0 the derivative is the one the reference's graph takes under TensorFlow 1.x's registered gradients (include/dcscn.h,
+// "ties"): prelu = relu(z) + a (z - |z|) / 2 gives a / 2, leaky_relu = maximum(z, 0.1 z) gives 1, selu gives the scale, relu gives 0.
+// prelu: the layer has a slope tensor; otherwise alpha is the constant slope, 0.1 (leaky_relu) or 0 (relu).
+__device__ inline float tact_grad(float z, float alpha, int act, bool prelu) {
     switch (act) {
-        case ACT_ALPHA:   return z > 0.0f ? 1.0f : alpha;
+        case ACT_ALPHA:   return z == 0.0f ? (prelu ? 0.5f * alpha : alpha > 0.0f ? 1.0f : 0.0f) : z > 0.0f ? 1.0f : alpha;
         case ACT_SIGMOID: { const float s = 1.0f / (1.0f + expf(-z)); return s * (1.0f - s); }
         case ACT_TANH:    { const float t = tanhf(z); return 1.0f - t * t; }
-        case ACT_SELU:    return z > 0.0f ? 1.0507009873554805f : 1.0507009873554805f * 1.6732632423543772f * expf(z);
+        case ACT_SELU:    return z >= 0.0f ? 1.0507009873554805f : 1.0507009873554805f * 1.6732632423543772f * expf(z);
         default:          return 1.0f;
     }
 }
@@ -249,7 +252,7 @@ __global__ void tact_bwd(const float* dh, int dh_stride, const float* z, int cou
     float g = dh[p * dh_stride + co];
     if (dropout) g = dropout_keep(lkey, idx0 + (uint64_t)e, thresh) ? g / keep : 0.0f;
     const float zz = z[e];
-    dz[e] = g * tact_grad(zz, alpha ? alpha[co] : calpha, act);
+    dz[e] = g * tact_grad(zz, alpha ? alpha[co] : calpha, act, alpha != nullptr);
     if (at) at[e] = g * (zz < 0.0f ? zz : 0.0f);
 }
 

@@ -427,6 +427,16 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  *   momentum: a <- mu a + g; w <- w - lr a  (not Nesterov)
  * Everything is deterministic: two identical sequences of calls give bit-identical variables and slots.
  *
+ * Ties.  At a pre-activation of exactly 0 the derivative of the activator is the one the reference's graph takes
+ * (helper/tf_graph.py:82-96) under TensorFlow 1.x's registered gradients:
+ *   prelu      = relu(z) + a (z - |z|) / 2   ReluGrad passes features > 0, Abs has the gradient sign(z) = 0       ->  a / 2
+ *   leaky_relu = maximum(z, 0.1 z)           MaximumGrad sends x >= y to the first argument                      ->  1
+ *   selu                                     SeluGrad: outputs < 0 ? g (outputs + scale alpha) : scale g         ->  1.0507009873554805
+ *   relu                                     ReluGrad                                                             ->  0
+ * and the gradient of a PReLU slope takes 0 from such an element.  The tie is an ordinary case: the reference initialises biases to
+ * zero, and a black image region then gives pre-activations of exactly 0 in every layer.  This convention is derived from the
+ * reference graph and those registrations; it has not been run against TensorFlow.
+ *
  * Dropout mask (not stored; regenerated by the backward pass).  With splitmix64(z) = { z += 0x9E3779B97F4A7C15;
  * z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31); } on uint64:
  *   layer_key = splitmix64(dropout_key + 0x9E3779B97F4A7C15 * (layer + 1))   layer = index in dcscn_layer_info order

@@ -30,20 +30,25 @@ def dropout_mask(key, layer, shape, keep):
 
 
 def _act(z, kind, alpha):
+    """The activators as the reference writes them (helper/tf_graph.py:82-96), so that autograd takes at z == 0 the gradient the
+    reference's graph takes under TensorFlow 1.x's registered gradients (ReluGrad: features > 0; Abs: sign(z); MaximumGrad: x >= y
+    goes to the first argument; SeluGrad: outputs < 0, else scale): a / 2 for prelu, 1 for leaky_relu, the scale for selu, 0 for relu.
+    This convention is derived from those registrations; it has not been run against TensorFlow.  For z != 0 the values and the
+    gradients are those of ``where(z > 0, z, a z)``: 2 z, its product with a and the halving are exact."""
     if kind is None or kind == "":
         return z
     if kind == "prelu":
-        return torch.where(z > 0, z, alpha.view(1, -1, 1, 1) * z)
+        return torch.relu(z) + alpha.view(1, -1, 1, 1) * (z - z.abs()) * 0.5
     if kind == "relu":
-        return torch.where(z > 0, z, torch.zeros_like(z))
+        return torch.relu(z)
     if kind == "leaky_relu":
-        return torch.where(z > 0, z, 0.1 * z)
+        return torch.where(z >= 0.1 * z, z, 0.1 * z)
     if kind == "sigmoid":
         return torch.sigmoid(z)
     if kind == "tanh":
         return torch.tanh(z)
     if kind == "selu":
-        return 1.0507009873554805 * torch.where(z > 0, z, 1.6732632423543772 * (torch.exp(torch.clamp(z, max=0)) - 1.0))
+        return 1.0507009873554805 * torch.where(z < 0, 1.6732632423543772 * (torch.exp(torch.clamp(z, max=0)) - 1.0), z)
     raise NameError(kind)
 
 
