@@ -7,7 +7,7 @@
 // order-independent, no atomics) and read from device memory by the consumers; the epilogue multiplies by 2^-(e_a + e_w) with ldexpf
 // (exact).  A non-finite input gives a non-finite result, as on the f32 path.
 //
-// The contract is tconv_gemm's (train.hip): SAME padding, stride 1, k order tap-major then channel-minor in chunks of 32 (a tap's channels
+// The contract is tconv_gemm's (train_kernels.hpp): SAME padding, stride 1, k order tap-major then channel-minor in chunks of 32 (a tap's channels
 // are padded to a multiple of 32 with zeros), bias added after the chain (ACCUM = 0) or out += result (ACCUM = 1), arbitrary in_stride /
 // out_stride slices, ragged pixel and channel counts masked to zero.
 #pragma once

@@ -3,7 +3,7 @@
 // ah*bh + ah*bl + al*bh per k-chunk of 32 pixels, accumulated in f32.  Both operands are scaled by train_h.hpp's power of two (max-abs into
 // [2^13, 2^14); the exponents are read from device memory) before they are split, and the epilogue undoes the scale with ldexpf (exact).
 //
-// The contract is tconv_wgrad's (train.hip): SAME padding, stride 1, ks 1 / 3 / 5 / 7, arbitrary in_stride and slice offset, ragged pixel,
+// The contract is tconv_wgrad's (train_kernels.hpp): SAME padding, stride 1, ks 1 / 3 / 5 / 7, arbitrary in_stride and slice offset, ragged pixel,
 // row and column counts masked to zero, a fixed partition of the pixels summed in a fixed order (no atomics: two runs give the same bits), a
 // non-finite input gives a non-finite result.  The partition differs from wgrad_splits': the unit is a TILE of tr rows x tc columns of one
 // image, tiles are numbered image-major, then row block, then column block, and split s sums tiles [s * tps, (s + 1) * tps) in that order.
