@@ -39,7 +39,7 @@ SOURCE_TABLE = {
     "conv5_h.hip": (KERNEL, True), "conv3_h_p16.hip": (KERNEL, True), "conv3_h8_p16.hip": (KERNEL, True),
     "conv3_h_fast16.hip": (KERNEL, True), "conv3_h8_fast16.hip": (KERNEL, True), "conv_nin_h_fast16.hip": (KERNEL, True),
     "conv5_h_fast16.hip": (KERNEL, True), "feat_stream_redo.hip": (NO_SLP, False), "feat3_stream.hip": (KERNEL, True),
-    "feat3_stream_fast16.hip": (KERNEL, True),
+    "feat3_stream_fast16.hip": (KERNEL, True), "feat_stream_fast16.hip": (KERNEL, True),
     "train.hip": ([], False), "train_data.hip": ([], False), "train_h.hip": (KERNEL, True),
     "train_wgrad_h.hip": (KERNEL, True),
 }

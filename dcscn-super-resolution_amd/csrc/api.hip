@@ -360,6 +360,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->fast16_stream = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "fast16_separable")) {         // any time, independent of both: picks the instantiation of the feat_stream / tail_stream launches
+        h->fast16_separable = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "train_split16")) {           // any time: the next gradient computation re-carves the training arena (train.hip: carve)
         h->train_split16 = value != 0;
         return DCSCN_OK;

@@ -222,7 +222,7 @@ static int launch_tail(dcscn_ctx* h, const Op& op, const Pass& p, bool stream16)
     a.blob = stream16 ? static_cast<const float*>(op.h16.d_w) : op.d_w;
     a.redo = redo_flags(h); a.redo_check = p.redo ? 1 : 0;
     const int grid = stream_geometry(a, p, 2, 256);
-    HIP_TRY(h, tail_launch(a, grid, stream16, p.stream));
+    HIP_TRY(h, tail_launch(a, grid, stream16, p.stream, h->split16 && h->fast16_separable));
     return DCSCN_OK;
 }
 
@@ -234,7 +234,7 @@ static int launch_stream(dcscn_ctx* h, const Op& op, const Pass& p, bool stream1
     a.blob = stream16 ? static_cast<const float*>(op.h16.d_w) : op.d_w;
     a.redo = redo_flags(h); a.redo_check = p.redo ? 1 : 0;
     const int grid = stream_geometry(a, p, a.L + 1, 256);
-    HIP_TRY(h, stream_launch(a, grid, stream16, p.stream));
+    HIP_TRY(h, stream_launch(a, grid, stream16, p.stream, h->split16 && h->fast16_separable));
     return DCSCN_OK;
 }
 
@@ -663,6 +663,7 @@ int run_forward(dcscn_ctx* h, const float* x, const float* x2, float* y, int n, 
     gkey.split16 = h->split16 ? h->split16_mask : 0;
     gkey.fast16 = h->split16 && h->fast16 ? 1 : 0;       // (picks the instantiation of every layer-kernel launch)
     gkey.fast16_stream = h->split16 && h->fast16_stream ? 1 : 0;      // (... and of the feat3_stream launch)
+    gkey.fast16_separable = h->split16 && h->fast16_separable ? 1 : 0;   // (... and of the feat_stream / tail_stream launches)
     gkey.nb = nb;                                        // the pass size (sub_batch_pixels / budget) shapes the launch sequence too
     gkey.h8 = h->conv3_h8 ? 1 : 0;
     gkey.nin_h8 = h->nin_h8 ? 1 : 0;

@@ -47,6 +47,11 @@ __device__ __forceinline__ void stream_barrier() { asm volatile("s_waitcnt lgkmc
 
 __device__ __forceinline__ f32x4 stream_ld(unsigned addr) { return *(stream_lds_rd)(uintptr_t)addr; }
 __device__ __forceinline__ void stream_st(unsigned addr, f32x4 v) { *(stream_lds_wr)(uintptr_t)addr = v; }
+// the first 8 bytes of a K = 16 filter slot [hi 0-3 | lo 0-3]: its hi half (one product per MAC reads nothing else)
+__device__ __forceinline__ h4 stream_ld_hi4(unsigned addr) {
+    typedef const __attribute__((address_space(3))) u32x2* lds_u2;
+    return __builtin_bit_cast(h4, *(lds_u2)(uintptr_t)addr);
+}
 
 // Decodes stream rows (all values are wave uniform).  A job = (image, row block, column strip); its rows are followed
 // by one separator row.  Rows are visited in increasing order, so the divisions run once per job.
@@ -217,9 +222,14 @@ template <int QL> struct StreamChunk {
 // meet zero filter rows.
 // F16: `init` is not read -- the bias (times 2^e) is fetched from LDS at the first MFMA (init_addr = address of tile 0's float4 of this
 // lane, tile n 64 bytes further): eight registers fewer across the depthwise part.
-template <int QUADS, int NT, int MT = kStreamMT, bool F16 = false>
+// NP = products per MAC of the F16 path (conv3_h.hpp, feat3_stream.hpp): 3 = split16 (wl * xh + wh * xl + wh * xh); 1 = option
+// "fast16_separable": wh * xh alone -- the depthwise output is converted to f16 (hi8 / hi4: no lo piece), the lo filter fragments are not
+// read, one MFMA per accumulator and chunk pair.  The filter image, the bias as C operand and the 2^-e scale are those of NP = 3.
+template <int QUADS, int NT, int MT = kStreamMT, bool F16 = false, int NP = 3>
 __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (&init)[NT], unsigned lds0, const unsigned (&rowb)[3], int dww, int wpo,
                                              int q, int lane, unsigned init_addr = 0) {
+    static_assert(NP == 1 || NP == 3, "one product (fast16_separable) or three (split16)");
+    static_assert(NP == 3 || F16, "one product per MAC is a form of the F16 path");
     constexpr int CH = (QUADS + 3) / 4;
     constexpr unsigned PX = (unsigned)(QUADS | 1) * 16u;
     f32x4 dpair[F16 ? MT : 1];                                // F16: the first chunk of a pair waits here for the second
@@ -286,7 +296,8 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
         }
         // (lanes of a missing quad hold the depthwise of a real one: finite, times zero filter rows)
         if constexpr (F16) {
-            const float m1 = opaque_minus_one();
+            [[maybe_unused]] float m1 = 0.0f;                 // (NP = 1: nothing is split)
+            if constexpr (NP == 3) m1 = opaque_minus_one();
             if constexpr ((ch & 1) == 0 && ch != CH - 1) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m) dpair[m] = d[m];
@@ -294,15 +305,19 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
                 constexpr bool first = ch == 1;
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    h8 bh, bl;
-                    split8(dpair[m], d[m], m1, bh, bl);
+                    h8 bh;
+                    [[maybe_unused]] h8 bl;
+                    if constexpr (NP == 3) split8(dpair[m], d[m], m1, bh, bl);
+                    else bh = hi8(dpair[m], d[m]);
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
                         const h8 ah = __builtin_bit_cast(h8, stream_ld(lds0 + wpo + (unsigned)(((ch - 1) * NT + 2 * n) * 64 + lane) * 16u));
-                        const h8 al = __builtin_bit_cast(h8, stream_ld(lds0 + wpo + (unsigned)(((ch - 1) * NT + 2 * n + 1) * 64 + lane) * 16u));
                         f32x4 c0 = first ? stream_ld(init_addr + (unsigned)n * 64u) : acc[m][n];
-                        c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c0, 0, 0, 0);
-                        c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c0, 0, 0, 0);
+                        if constexpr (NP == 3) {
+                            const h8 al = __builtin_bit_cast(h8, stream_ld(lds0 + wpo + (unsigned)(((ch - 1) * NT + 2 * n + 1) * 64 + lane) * 16u));
+                            c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c0, 0, 0, 0);
+                            c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c0, 0, 0, 0);
+                        }
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c0, 0, 0, 0);
                     }
                 }
@@ -310,16 +325,25 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
                 constexpr bool first = ch == 0;
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-                    h4 bh, bl;
-                    split4(d[m], m1, bh, bl);
+                    h4 bh;
+                    [[maybe_unused]] h4 bl;
+                    if constexpr (NP == 3) split4(d[m], m1, bh, bl);
+                    else bh = hi4(d[m]);
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
-                        const f32x4 wv = stream_ld(lds0 + wpo + (unsigned)((ch * NT + n) * 64 + lane) * 16u);
-                        const u32x4 wu = __builtin_bit_cast(u32x4, wv);
-                        const h4 ah = __builtin_bit_cast(h4, u32x2{wu.x, wu.y}), al = __builtin_bit_cast(h4, u32x2{wu.z, wu.w});
+                        const unsigned wa = lds0 + wpo + (unsigned)((ch * NT + n) * 64 + lane) * 16u;
+                        [[maybe_unused]] u32x4 wu;
+                        h4 ah;
+                        if constexpr (NP == 3) {
+                            wu = __builtin_bit_cast(u32x4, stream_ld(wa));
+                            ah = __builtin_bit_cast(h4, u32x2{wu.x, wu.y});
+                        } else ah = stream_ld_hi4(wa);        // (the hi half of the slot alone)
                         f32x4 c0 = first ? stream_ld(init_addr + (unsigned)n * 64u) : acc[m][n];
-                        c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(al, bh, c0, 0, 0, 0);
-                        c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bl, c0, 0, 0, 0);
+                        if constexpr (NP == 3) {
+                            const h4 al = __builtin_bit_cast(h4, u32x2{wu.z, wu.w});
+                            c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(al, bh, c0, 0, 0, 0);
+                            c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bl, c0, 0, 0, 0);
+                        }
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bh, c0, 0, 0, 0);
                     }
                 }
@@ -341,7 +365,7 @@ __device__ __forceinline__ void stream_dw_pw(f32x4 (&acc)[MT][NT], const f32x4 (
 
 // ---- CNN2 .. CNNL, B2: depthwise 3x3 from the predecessor's ring -> pointwise GEMM -> bias, PReLU -----------------
 // QUADS = channel quads of the input, NT = 16-channel tiles of the output (compile time: no branches between the MFMAs)
-template <int QUADS, int NT, bool F16, bool GATE>
+template <int QUADS, int NT, bool F16, bool GATE, int NP = 3>
 __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const StreamConv& c, unsigned lds0, int j0, int rows, int T, int lane) {
     const int j = lane & 15, q = lane >> 4;
     const float zflag = opaque_zero();
@@ -364,7 +388,7 @@ __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const Stre
 #pragma unroll
                     for (int n = 0; n < NT; ++n) bs[n] = stream_ld(lds0 + c.ba + (unsigned)(n * 4 + q) * 16u);
                 }
-                stream_dw_pw<QUADS, NT, kStreamMT, F16>(acc, bs, lds0, rowb, c.dww, c.wp, q, lane, lds0 + c.ba + (unsigned)q * 16u);
+                stream_dw_pw<QUADS, NT, kStreamMT, F16, NP>(acc, bs, lds0, rowb, c.dww, c.wp, q, lane, lds0 + c.ba + (unsigned)q * 16u);
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     const f32x4 al = stream_ld(lds0 + c.ba + 128u + (unsigned)(n * 4 + q) * 16u);
@@ -412,7 +436,7 @@ __device__ __forceinline__ void stream_conv_role(const StreamArgs& a, const Stre
 }
 
 // ---- A1 || B1: one (feature layer, row) contribution per step and wave --------------------------------------------
-template <bool F16, bool GATE>
+template <bool F16, bool GATE, int NP = 3>
 __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsigned lds0, int j0, int rows, int T, int) {
     const int L = a.L;
     const float zflag = opaque_zero();
@@ -447,8 +471,10 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
                     const unsigned rowb = lds0 + s.ring.off + ((unsigned)(g % 3) * kStreamRowPx + 3 * j + 1) * (unsigned)s.ring.units * 16u;
                     if constexpr (F16) {
                         // chunk pairs on v_mfma_f32_16x16x32_f16, an odd last chunk on the K = 16 form (stream_dw_pw, F16); a short last
-                        // chunk's missing quads read a valid one against zero filter rows
-                        const float m1 = opaque_minus_one();
+                        // chunk's missing quads read a valid one against zero filter rows.  NP = 1 (stream_dw_pw): the ring value is converted,
+                        // not split, the lo fragments are not read and each accumulator takes one MFMA
+                        [[maybe_unused]] float m1 = 0.0f;
+                        if constexpr (NP == 3) m1 = opaque_minus_one();
                         const int lql = s.last_ql;
                         const int lcq = lql >= 3 ? min(q, lql - 1) : lql == 2 ? (q & 1) : 0;
 #pragma unroll 1
@@ -458,15 +484,22 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
 #pragma unroll
                             for (int m = 0; m < kStreamMT; ++m) {
                                 const f32x4 x0 = stream_ld(rowb + (unsigned)(m * s.ring.units) * 16u + q0), x1 = stream_ld(rowb + (unsigned)(m * s.ring.units) * 16u + q1);
-                                h8 bh, bl;
-                                split8(x0, x1, m1, bh, bl);
+                                h8 bh;
+                                [[maybe_unused]] h8 bl;
+                                if constexpr (NP == 3) split8(x0, x1, m1, bh, bl);
+                                else bh = hi8(x0, x1);
                                 // (the fragments of one tile at a time, re-read per pixel tile: LDS reads are free beside f16 MFMAs, registers are not)
 #pragma unroll
                                 for (int n = 0; n < 2; ++n) {
+                                    if constexpr (NP == 3) {
                                     const h8 ah = __builtin_bit_cast(h8, stream_ld(wb + (unsigned)n * 2048u)), al = __builtin_bit_cast(h8, stream_ld(wb + (unsigned)n * 2048u + 1024u));
                                     acc[p][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[p][m][n], 0, 0, 0);
                                     acc[p][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc[p][m][n], 0, 0, 0);
                                     acc[p][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[p][m][n], 0, 0, 0);
+                                    } else {
+                                        const h8 ah = __builtin_bit_cast(h8, stream_ld(wb + (unsigned)n * 2048u));
+                                        acc[p][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[p][m][n], 0, 0, 0);
+                                    }
                                     asm volatile("" ::: "memory");
                                 }
                             }
@@ -474,6 +507,16 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
                         if (s.chunks & 1) {
                             const int ch = s.chunks - 1;
                             const unsigned qo = (unsigned)(4 * ch + lcq) * 16u;
+                            if constexpr (NP == 1) {
+                                const h4 a0h = stream_ld_hi4(lds0 + s.w + (unsigned)((ch * 2 + 0) * 64 + lane) * 16u);
+                                const h4 a1h = stream_ld_hi4(lds0 + s.w + (unsigned)((ch * 2 + 1) * 64 + lane) * 16u);
+#pragma unroll
+                                for (int m = 0; m < kStreamMT; ++m) {
+                                    const h4 bh = hi4(stream_ld(rowb + (unsigned)(m * s.ring.units) * 16u + qo));
+                                    acc[p][m][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a0h, bh, acc[p][m][0], 0, 0, 0);
+                                    acc[p][m][1] = __builtin_amdgcn_mfma_f32_16x16x16f16(a1h, bh, acc[p][m][1], 0, 0, 0);
+                                }
+                            } else {
                             const u32x4 w0 = __builtin_bit_cast(u32x4, stream_ld(lds0 + s.w + (unsigned)((ch * 2 + 0) * 64 + lane) * 16u));
                             const u32x4 w1 = __builtin_bit_cast(u32x4, stream_ld(lds0 + s.w + (unsigned)((ch * 2 + 1) * 64 + lane) * 16u));
                             const h4 a0h = __builtin_bit_cast(h4, u32x2{w0.x, w0.y}), a0l = __builtin_bit_cast(h4, u32x2{w0.z, w0.w});
@@ -489,6 +532,7 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
                                 c1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1h, bl, c1, 0, 0, 0);
                                 acc[p][m][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a0h, bh, c0, 0, 0, 0);
                                 acc[p][m][1] = __builtin_amdgcn_mfma_f32_16x16x16f16(a1h, bh, c1, 0, 0, 0);
+                            }
                             }
                         }
                     } else
@@ -567,9 +611,10 @@ __device__ __forceinline__ void stream_nin_role(const StreamArgs& a, int w, unsi
 }
 
 // F16 = the pointwise GEMMs and A1 || B1 on the f16 matrix pipe (stream_dw_pw); false = v_mfma_f32_16x16x4_f32 (split16 = 0).
+// NP = products per MAC of the F16 path: 3, or 1 = option "fast16_separable" (feat_stream_fast16.hip); CNN1 is f32 VALU work either way.
 // GATE = the float32 plan of flagged images (F16 = false): leaves at once unless the pass flagged an image, stores only flagged images --
 // its own instantiation, so that the kernels of every pass carry none of it (they sit at their 128-register cap)
-template <bool F16, bool GATE = false>
+template <bool F16, bool GATE = false, int NP = 3>
 __global__ __launch_bounds__(1024) void feat_stream(const StreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (GATE && a.redo[0] == 0) return;
@@ -594,16 +639,16 @@ __global__ __launch_bounds__(1024) void feat_stream(const StreamArgs a) {
         // the instantiated (input quads, output tiles) pairs -- api.hip: stream_conv_supported
         const bool nt2 = c.out.quads > 4;
         switch (c.in.quads) {
-            case 1: stream_conv_role<1, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 2: stream_conv_role<2, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 3: stream_conv_role<3, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 4: stream_conv_role<4, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 5: stream_conv_role<5, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 6: stream_conv_role<6, 2, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            case 7: stream_conv_role<7, 2, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
-            default: if (nt2) stream_conv_role<8, 2, F16, GATE>(a, c, lds0, j0, rows, T, lane); else stream_conv_role<8, 1, F16, GATE>(a, c, lds0, j0, rows, T, lane); break;
+            case 1: stream_conv_role<1, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 2: stream_conv_role<2, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 3: stream_conv_role<3, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 4: stream_conv_role<4, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 5: stream_conv_role<5, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 6: stream_conv_role<6, 2, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            case 7: stream_conv_role<7, 2, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
+            default: if (nt2) stream_conv_role<8, 2, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); else stream_conv_role<8, 1, F16, GATE, NP>(a, c, lds0, j0, rows, T, lane); break;
         }
-    } else stream_nin_role<F16, GATE>(a, role - 16, lds0, j0, rows, T, lane);
+    } else stream_nin_role<F16, GATE, NP>(a, role - 16, lds0, j0, rows, T, lane);
 }
 
 }  // namespace dcscn

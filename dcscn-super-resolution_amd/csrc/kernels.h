@@ -247,10 +247,12 @@ struct TailArgs {
     int32_t* redo;        // as StreamArgs
     int32_t redo_check;
 };
-// f16 = the F16 instantiation (a.blob = the f16 image of the filters: pack.hip)
-hipError_t tail_launch(const TailArgs& a, int grid, bool f16, hipStream_t stream);
+// f16 = the F16 instantiation (a.blob = the f16 image of the filters: pack.hip); fast16 (option "fast16_separable", with f16 only): its
+// one-product form (feat_stream.hpp: NP = 1; feat_stream_fast16.hip) on the same arguments and the same image.  The float32 plan
+// (redo_check) is the gated float32 instantiation whatever the two say.
+hipError_t tail_launch(const TailArgs& a, int grid, bool f16, hipStream_t stream, bool fast16 = false);
 void stream_init_kernels();
-hipError_t stream_launch(const StreamArgs& a, int grid, bool f16, hipStream_t stream);
+hipError_t stream_launch(const StreamArgs& a, int grid, bool f16, hipStream_t stream, bool fast16 = false);
 
 // ---- row-streamed feature extractor of the NON-separable narrow nets (feat3_stream.hpp) ----
 constexpr int kS3MaxL = 8;         // feature layers

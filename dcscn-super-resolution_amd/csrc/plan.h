@@ -218,11 +218,11 @@ struct dcscn_ctx {
     struct GraphKey {
         const void *x = nullptr, *x2 = nullptr, *y = nullptr;
         void* stream = nullptr;
-        int n = 0, H = 0, W = 0, split16 = 0, fast16 = 0, fast16_stream = 0, nb = 0, h8 = 0, nin_h8 = 0, p16 = 0;
+        int n = 0, H = 0, W = 0, split16 = 0, fast16 = 0, fast16_stream = 0, fast16_separable = 0, nb = 0, h8 = 0, nin_h8 = 0, p16 = 0;
         unsigned long long carve = 0;
         bool operator==(const GraphKey& o) const {
             return x == o.x && x2 == o.x2 && y == o.y && stream == o.stream && n == o.n && H == o.H && W == o.W && split16 == o.split16 && fast16 == o.fast16 &&
-                   fast16_stream == o.fast16_stream && nb == o.nb &&
+                   fast16_stream == o.fast16_stream && fast16_separable == o.fast16_separable && nb == o.nb &&
                    h8 == o.h8 && nin_h8 == o.nin_h8 && p16 == o.p16 && carve == o.carve;
         }
     };
@@ -239,6 +239,8 @@ struct dcscn_ctx {
                                              // conv3_h.hpp: NP = 1) -- f16 accuracy of the operands, f32 accumulation; ignored with split16 = 0 and by the streamed kernels
     bool fast16_stream = false;              // option "fast16_stream": the same for the MFMA contractions of a feat3_stream launch (feat3_stream.hpp: NP = 1); independent of
                                              // "fast16"; ignored with split16 = 0 and where the plan has no such launch
+    bool fast16_separable = false;           // option "fast16_separable": the same for the MFMA contractions of the separable nets' feat_stream / tail_stream launches
+                                             // (feat_stream.hpp: NP = 1); independent of the two above; ignored with split16 = 0 and where the plan has no such launch
     size_t redo_off = 0, redo_ints = 0;      // redo flags of a pass inside the arena (byte offset, count = 1 + images): [0] any, [1 + image]
     bool p16 = true;                         // option "p16": tensors between split16 launches are kept pre-split (p16.hpp) where plan_p16 allows
     bool p16_now = false;                    // the current carve holds them so (split16 on for both kernel families and p16)

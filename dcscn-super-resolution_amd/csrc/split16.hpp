@@ -65,6 +65,23 @@ __device__ __forceinline__ void split8(const f32x4 x, const f32x4 y, float m1, h
     lo = __builtin_bit_cast(h8, l);
 }
 
+// The convert-only companions of split4 / split8 (one product per MAC: option "fast16_separable"): the hi piece alone, one
+// v_cvt_pk_f16_f32 per two values and no lo piece.  The same conversion split2 starts from, so the same bits as its hi.
+__device__ __forceinline__ unsigned hi2(float x0, float x1) {
+    const h2 p = {(_Float16)x0, (_Float16)x1};
+    return __builtin_bit_cast(unsigned, p);
+}
+
+__device__ __forceinline__ h4 hi4(const f32x4 x) {
+    const u32x2 h = {hi2(x.x, x.y), hi2(x.z, x.w)};
+    return __builtin_bit_cast(h4, h);
+}
+
+__device__ __forceinline__ h8 hi8(const f32x4 x, const f32x4 y) {
+    const u32x4 h = {hi2(x.x, x.y), hi2(x.z, x.w), hi2(y.x, y.y), hi2(y.z, y.w)};
+    return __builtin_bit_cast(h8, h);
+}
+
 __device__ __forceinline__ float opaque_minus_one() {
     float m1 = -1.0f;
     asm volatile("" : "+s"(m1));                // a scalar register: the fma takes it as its one SGPR operand

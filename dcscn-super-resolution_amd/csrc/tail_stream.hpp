@@ -76,7 +76,7 @@ __device__ __forceinline__ void tail_load_role(const TailArgs& a, const StreamAr
 // ---- Up-PS on 16 pixels, all four sub-pixel phases ------------------------------------------------------------------------
 // (splitting by phase instead would make four waves repeat the same depthwise; here a lane owns ONE pixel, its window is 3
 // reads per row, and the wave runs the whole [4C x C] pointwise: 8 channel tiles of accumulators)
-template <int QI, bool F16>
+template <int QI, bool F16, int NP = 3>
 __device__ __forceinline__ void tail_up1_role(const TailArgs& a, const StreamArgs& geo, int seg, unsigned lds0, int j0, int rows, int T, int lane) {
     const int j = lane & 15, q = lane >> 4;
     constexpr unsigned in_px = (unsigned)(QI | 1) * 16u, in_row = (unsigned)kStreamRowPx * in_px;
@@ -101,7 +101,7 @@ __device__ __forceinline__ void tail_up1_role(const TailArgs& a, const StreamArg
 #pragma unroll
                     for (int n = 0; n < 8; ++n) bs[n] = stream_ld(lds0 + a.a_bias + (unsigned)(n * 4 + q) * 16u);
                 }
-                stream_dw_pw<QI, 8, 1, F16>(acc, bs, lds0, rowb, a.a_dww, a.a_wp, q, lane, lds0 + a.a_bias + (unsigned)q * 16u);
+                stream_dw_pw<QI, 8, 1, F16, NP>(acc, bs, lds0, rowb, a.a_dww, a.a_wp, q, lane, lds0 + a.a_bias + (unsigned)q * 16u);
                 if constexpr (F16) {
 #pragma unroll
                     for (int n = 0; n < 8; ++n) acc[0][n] = acc[0][n] * a.a_inv;
@@ -130,7 +130,7 @@ __device__ __forceinline__ void tail_up1_role(const TailArgs& a, const StreamArg
 }
 
 // ---- Up-PS2 on U row 2g + r2, pixels 48 * half .. + 47 ------------------------------------------------------------------
-template <int QU, bool F16>
+template <int QU, bool F16, int NP = 3>
 __device__ __forceinline__ void tail_up2_role(const TailArgs& a, const StreamArgs& geo, int r2, int half, unsigned lds0, int j0, int rows, int T, int lane) {
     const int j = lane & 15, q = lane >> 4;
     constexpr unsigned u_px = (unsigned)(QU | 1) * 16u, u_row = (unsigned)kTailURowPx * u_px;
@@ -150,7 +150,7 @@ __device__ __forceinline__ void tail_up2_role(const TailArgs& a, const StreamArg
                 for (int dy = 0; dy < 3; ++dy)
                     rowb[dy] = lds0 + a.u.off + (unsigned)((ur - 1 + dy + kTailUSlots) % kTailUSlots) * u_row + (unsigned)(kStreamPX * half + 3 * j) * u_px;
                 const f32x4 bs[1] = {F16 ? kStreamZero : stream_ld(lds0 + a.b_bias)};
-                stream_dw_pw<QU, 1, kStreamMT, F16>(acc, bs, lds0, rowb, a.b_dww, a.b_wp, q, lane, lds0 + a.b_bias);
+                stream_dw_pw<QU, 1, kStreamMT, F16, NP>(acc, bs, lds0, rowb, a.b_dww, a.b_wp, q, lane, lds0 + a.b_bias);
                 if constexpr (F16) {
 #pragma unroll
                     for (int m = 0; m < kStreamMT; ++m) acc[m][0] = acc[m][0] * a.b_inv;
@@ -251,7 +251,8 @@ __device__ __forceinline__ void tail_rec_role(const TailArgs& a, const StreamArg
 }
 
 // F16: the two pointwise GEMMs on the f16 matrix pipe (feat_stream.hpp: stream_dw_pw); false: f32 MFMAs, and the float32 plan (redo_check)
-template <bool F16, bool GATE = false>
+// NP: products per MAC of the F16 path, 3 or 1 (option "fast16_separable", feat_stream_fast16.hip); R-CNN1 is f32 VALU work either way
+template <bool F16, bool GATE = false, int NP = 3>
 __global__ __launch_bounds__(640) void tail_stream(const TailArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (GATE && a.redo[0] == 0) return;
@@ -276,8 +277,8 @@ __global__ __launch_bounds__(640) void tail_stream(const TailArgs a) {
     constexpr int kRole[10] = {4, 1, 2, 3, 5, 8, 6, 7, 0, 9};
     const int role = kRole[wave];
     if (role == 0) tail_load_role(a, geo, lds0, j0, rows, T, lane);
-    else if (role <= 3) tail_up1_role<8, F16>(a, geo, role - 1, lds0, j0, rows, T, lane);      // instantiated for 32 -> 4 x 32 -> 4 channels (api.hip: fuse_tail_stream)
-    else if (role <= 7) tail_up2_role<8, F16>(a, geo, (role - 4) >> 1, (role - 4) & 1, lds0, j0, rows, T, lane);
+    else if (role <= 3) tail_up1_role<8, F16, NP>(a, geo, role - 1, lds0, j0, rows, T, lane);      // instantiated for 32 -> 4 x 32 -> 4 channels (api.hip: fuse_tail_stream)
+    else if (role <= 7) tail_up2_role<8, F16, NP>(a, geo, (role - 4) >> 1, (role - 4) & 1, lds0, j0, rows, T, lane);
     else tail_rec_role<F16, GATE>(a, geo, role - 8, lds0, j0, rows, T, lane);
 }
 

@@ -94,6 +94,8 @@ class SuperResolution:
         self.fast16 = bool(getattr(flags, "fast16", False))
         # extension: ... and the streamed feature extractor of the narrow nets too (engine option "fast16_stream"), independently
         self.fast16_stream = bool(getattr(flags, "fast16_stream", False))
+        # extension: ... and the streamed kernels of the separable narrow nets (engine option "fast16_separable"), independently of both
+        self.fast16_separable = bool(getattr(flags, "fast16_separable", False))
         # extension: training takes the wide layers' forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16")
         self.train_split16 = bool(getattr(flags, "train_split16", False))
         # extension: ... and their weight gradients (engine option "train_split16_wgrad"), independently
@@ -214,6 +216,8 @@ class SuperResolution:
             self._engine.set_option("fast16", 1)
         if self.fast16_stream:
             self._engine.set_option("fast16_stream", 1)
+        if self.fast16_separable:
+            self._engine.set_option("fast16_separable", 1)
         self._weights = None
         return self._engine
 

@@ -92,6 +92,8 @@ _TABLE = [
     (_B, "fast16", False, "inference at f16 operand accuracy: one matrix product per MAC instead of three (training is unaffected)"),
     # ---- extension (not a reference flag): the same inside the narrow nets' streamed feature extractor (engine option "fast16_stream", include/dcscn.h)
     (_B, "fast16_stream", False, "inference with one f16 product per MAC inside the streamed feature extractor of the narrow nets (c-DCSCN); independent of --fast16"),
+    # ---- extension (not a reference flag): the same inside the separable narrow nets' streamed kernels (engine option "fast16_separable", include/dcscn.h)
+    (_B, "fast16_separable", False, "inference with one f16 product per MAC inside the streamed kernels of the depthwise-separable narrow nets (feat_stream, tail_stream); independent of --fast16 and --fast16_stream"),
     # ---- extension (not a reference flag): training's wide forward / data-gradient convs on the f16 matrix pipe (engine option "train_split16", include/dcscn.h)
     (_B, "train_split16", False, "training at f32 accuracy with the forward and data-gradient convs of layers with min(cin, cout) >= 16 as three scaled f16 products"),
     # ---- extension (not a reference flag): the weight gradients of the same layers on the f16 matrix pipe (engine option "train_split16_wgrad", include/dcscn.h)

@@ -243,6 +243,17 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * stream_nin = 0, the tail kernels and a later fast16_stream = 0 read what they always read), and scale, bias, PReLU, the redo flags and
  * the gated float32 plan are split16's.  Ignored where the plan has no feat3_stream launch: split16 = 0, stream_dense = 0, the wide nets,
  * and the separable nets' feat_stream / tail_stream, which keep three products.  Error and speed: DESIGN.md 3.13.
+ * "fast16_separable" (default 0; any time, like "fast16", and independent of it and of "fast16_stream": every combination is legal): the
+ * same mode for the feat_stream and tail_stream launches of the depthwise-separable narrow nets, which the two options above leave on
+ * three products.  With 1, every matrix contraction inside such a launch -- the pointwise stage of CNN2 .. CNNL and B2, A1 || B1, and in
+ * tail_stream Up-PS and Up-PS2 -- is the single product wh * xh: xh = f16 (round to nearest even) of the f32 value the lane holds (the
+ * depthwise output; for A1 || B1 the ring value), wh = the `hi` half of the scaled f16 filter image, accumulated in f32; the `lo` halves
+ * of the activations are not computed, the `lo` filter fragments not loaded and the two cross products not issued.  CNN1 and R-CNN1 stay
+ * f32 VALU work, the depthwise stage stays f32, the filter blob still holds (hi | lo) (a later fast16_separable = 0 reads what it always
+ * read), and bias, the 2^-e scale, PReLU, the rings, the redo flags and the gated float32 plan are split16's -- a flagged image is still
+ * recomputed to the bits of a split16 = 0 run.  Ignored where the plan has no such launch: split16 = 0, stream_features = 0 /
+ * stream_tail = 0, widths feat_stream does not take, every non-separable net, and the layer-by-layer separable kernels (depthwise,
+ * conv_igemm with a fused depthwise stage).  Error and speed: DESIGN.md 3.13.
  * "train_split16" (default 0; any time, also before dcscn_train_begin; takes effect from the next gradient computation, which re-carves
  * the training workspace): an opt-in training mode at the f32 path's accuracy.  With 1, every layer of the training plan with
  * min(cin, cout) >= 16 -- a rule of the layer's shape alone, the same for both directions -- takes its forward conv and its data-gradient

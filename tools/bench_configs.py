@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Throughput of the other BASELINE.json configurations (bench.py measures configs[2]):
    python tools/bench_configs.py [--steps 5]   -> one line per config, per-launch table with --ops.
-   --fast16: every config is timed with the options (fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) ALTERNATING in one process
-   (--rounds blocks of --steps passes each, median block per setting), one line per setting plus their ratios; with --ops the per-launch
-   times of the settings side by side and the feat3_stream launch's own time per setting."""
+   --fast16: every config is timed with the options (fast16, S) = (0,0), (1,0), (0,1), (1,1) ALTERNATING in one process, S being the
+   streamed kernels' own option -- fast16_stream where the plan has a feat3_stream launch, fast16_separable where it has a feat_stream
+   or tail_stream launch (the separable configs) -- (--rounds blocks of --steps passes each, median block per setting), one line per
+   setting plus their ratios; with --ops the per-launch times of the settings side by side and the streamed launches' own times per setting.
+   --set KEY=VALUE (repeatable): engine options set before the weights are loaded, e.g. --set fold_whole_tail=0 for C5 with tail_stream."""
 import argparse
 import os
 import sys
@@ -27,31 +29,37 @@ CONFIGS = [
 ]
 
 
-SETTINGS = ((0, 0), (1, 0), (0, 1), (1, 1))           # (fast16, fast16_stream)
+SETTINGS = ((0, 0), (1, 0), (0, 1), (1, 1))           # (fast16, the streamed kernels' option)
+STREAM_OPTION = {"feat3_stream": "fast16_stream", "feat_stream": "fast16_separable", "tail_stream": "fast16_separable"}
 
 
-def _set(eng, setting):
+def _set(eng, setting, key):
     eng.set_option("fast16", setting[0])
-    eng.set_option("fast16_stream", setting[1])
+    if key:
+        eng.set_option(key, setting[1])
 
 
 def fast16_compare(args, name, eng, torch, io):
-    """(fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) in alternating blocks of args.steps passes on one handle; median block per
-    setting.  A plan without a feat3_stream launch ignores fast16_stream: only the first two settings are timed there."""
+    """(fast16, S) = (0,0), (1,0), (0,1), (1,1) in alternating blocks of args.steps passes on one handle; median block per setting.  S is
+    fast16_stream or fast16_separable, whichever governs the plan's streamed launches; a plan without one ignores both: only the first two
+    settings are timed there."""
     x, x2, y, n, st = io
     run = lambda: eng.forward_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, 48, 48, st)
-    streamed = [i for i, o in enumerate(eng.ops()) if o["kernel"] == "feat3_stream"]
+    streamed = [i for i, o in enumerate(eng.ops()) if o["kernel"] in STREAM_OPTION]
+    keys = sorted({STREAM_OPTION[eng.ops()[i]["kernel"]] for i in streamed})
+    assert len(keys) <= 1, keys
+    key = keys[0] if keys else None
     settings = SETTINGS if streamed else SETTINGS[:2]
-    tag = lambda v: "fast16 %d fast16_stream %d" % v
+    tag = lambda v: "fast16 %d %s %d" % (v[0], key or "fast16_stream", v[1])
     for v in settings:                                 # warm every setting (and capture its graph with --graph)
-        _set(eng, v)
+        _set(eng, v, key)
         for _ in range(3):
             run()
     torch.cuda.synchronize()
     times = {v: [] for v in settings}
     for _ in range(args.rounds):
         for v in settings:
-            _set(eng, v)
+            _set(eng, v, key)
             run()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -72,7 +80,7 @@ def fast16_compare(args, name, eng, torch, io):
         rows = {v: [] for v in settings}
         for _ in range(args.steps):                    # alternating here too: one profiled pass per setting and round
             for v in settings:
-                _set(eng, v)
+                _set(eng, v, key)
                 run()
                 torch.cuda.synchronize()
                 rows[v].append(eng.profile())
@@ -86,7 +94,7 @@ def fast16_compare(args, name, eng, torch, io):
                   + "  ratio to (0,0) " + " ".join("%.3f" % (per[v][i] / base if base else 0) for v in settings[1:]))
         print("    %-26s " % "sum of launches" + "  ".join("(%d,%d) %7.3f ms" % (v + (sum(per[v]),)) for v in settings), flush=True)
         for i in streamed:                             # the streamed launch's own time per setting
-            print("    feat3_stream launch %-22s " % eng.ops()[i]["name"] + "  ".join("(%d,%d) %7.3f ms" % (v + (per[v][i],)) for v in settings)
+            print("    %s launch %-22s " % (eng.ops()[i]["kernel"], eng.ops()[i]["name"]) + "  ".join("(%d,%d) %7.3f ms" % (v + (per[v][i],)) for v in settings)
                   + "  (0,1) / (0,0) = %.4f  (1,1) / (1,0) = %.4f" % (per[(0, 1)][i] / per[(0, 0)][i], per[(1, 1)][i] / per[(1, 0)][i]), flush=True)
 
 
@@ -96,7 +104,8 @@ def main():
     ap.add_argument("--ops", action="store_true")
     ap.add_argument("--only", default="")
     ap.add_argument("--graph", action="store_true", help="option graph_replay: the pass replayed from a hipGraph")
-    ap.add_argument("--fast16", action="store_true", help="time (fast16, fast16_stream) = (0,0), (1,0), (0,1), (1,1) alternating in one process and print the ratios")
+    ap.add_argument("--fast16", action="store_true", help="time (fast16, fast16_stream or fast16_separable) = (0,0), (1,0), (0,1), (1,1) alternating in one process and print the ratios")
+    ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="engine option set before the weights are loaded (repeatable)")
     ap.add_argument("--rounds", type=int, default=7, help="--fast16: timed blocks per setting")
     args = ap.parse_args()
     import torch
@@ -107,6 +116,10 @@ def main():
             continue
         cfg = O.make_config(**flags)
         eng = engine.Engine(cfg)
+        for kv in args.set:
+            k, v = kv.split("=")
+            eng.set_option(k, int(v))
+            name = "%s %s" % (name, kv)
         eng.load_weights(O.synthetic_weights(cfg, seed=0))
         s = cfg["scale"]
         x = torch.rand((n, 48, 48, 1), device="cuda") * 255
