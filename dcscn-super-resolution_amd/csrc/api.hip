@@ -372,6 +372,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->train_split16_wgrad = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "train_separable")) {          // read by dcscn_train_begin alone: no effect on a non-separable net, none after it
+        h->train_separable = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
         h->p16 = value != 0;
         return DCSCN_OK;

@@ -1,4 +1,5 @@
-// Single-GPU f32 training of the non-separable pixel-shuffler DCSCN nets (DCSCN.py:334-425, tf_graph.py:117-153).
+// Single-GPU f32 training of the pixel-shuffler DCSCN nets (DCSCN.py:334-425, tf_graph.py:117-177); the depthwise-separable ones behind
+// option "train_separable".
 //
 // The training plan is its own list of layers over its own arena (TrainState); it shares only the variables with the inference
 // plan.  Every conv runs as one launch of tconv_gemm (implicit GEMM on v_mfma_f32_16x16x4_f32, rows = output pixels, columns =
@@ -9,12 +10,19 @@
 // layout, so neither direction copies.  Every reduction is a fixed partition summed in a fixed order: no atomics anywhere, two
 // identical runs give identical bits.
 //
+// A separable conv layer (tf.nn.separable_conv2d) is two stages: the depthwise k x k conv into a dense tensor d kept for the backward
+// (tdw_fwd, train_dw.hpp), then all of the above with ks = 1 on d and the pointwise filter.  Backward: the pointwise weight gradient from d,
+// dd = dz . P^T into a scratch by the data-gradient filter, the depthwise weight gradient from the layer's input and dd (tdw_wgrad over a fixed
+// pixel split, summed by treduce_wgrad), and tdw_dgrad accumulating into the gradient of the layer's input.  Neither filter of a separable
+// layer is in the l2 term (the reference sums l2_loss over the layer's unused conv_W instead): no decay in their gradients.
+//
 // Variables, their gradients and the optimizer slots live in flat f32 buffers in the checkpoint (HWIO) layout, in the order of
 // the graph's variable list (dcscn_tensor_info), so the update is one elementwise launch.
 #include "plan.h"
 #include "train_h.hpp"
 #include "train_wgrad_h.hpp"
 #include "train_kernels.hpp"   // the kernels, and fp contract(off) for them and everything below
+#include "train_dw.hpp"
 
 namespace dcscn_impl {
 
@@ -33,11 +41,16 @@ struct TLayer {
     int out_buf = -1, out_off = 0; // activation destination (act layers) / depth_to_space destination (ps > 0); -1: y_ (last layer)
     int ps = 0;                    // > 0: Up-PS conv followed by depth_to_space with this factor
     int w_t = -1, b_t = -1, a_t = -1;
+    bool ds = false;               // a separable layer: ks is the depthwise filter's, w_t the pointwise filter [cin][cout], and the convs run with ks = 1 on d
+    int dw_t = -1;                 // ... its depthwise filter [ks][ks][cin][1]
     float* z = nullptr;            // pre-activation, dense [px, cout]
+    float* d = nullptr;            // separable: the depthwise stage's output, dense [px, cin]
     // ---- the launch plan of the current carve: all that the batch shape and the two options fix (plan_layer); run_gradients only reads it ----
     int Hr = 0, Wr = 0;            // the batch's H and W at the layer's resolution
     int64_t px = 0;                // n Hr Wr pixels
-    int64_t zcount = 0, wcount = 0;   // elements of z (px cout) and of the filter (ks ks cin cout)
+    int64_t zcount = 0, wcount = 0;   // elements of z (px cout) and of the filter (ks ks cin cout; separable: the pointwise filter's cin cout)
+    int64_t dcount = 0, dwcount = 0;  // separable: elements of d (px cin) and of the depthwise filter (ks ks cin)
+    int dws = 0, dcw = 0; int64_t dchunk = 0;   // dw_splits: the depthwise weight gradient
     // option "train_split16" (train_h.hpp): h16 = the layer's forward and data-gradient convs run on tconv_gemm_h
     bool h16 = false;
     void *w16 = nullptr, *wd16 = nullptr;   // tpack_h images: forward, data gradient (null for a layer on the network input)
@@ -49,6 +62,7 @@ struct TLayer {
     int64_t chunk = 0;
     TWgradHPlan wp{};
     int cs = 0; int64_t cchunk = 0;   // col_splits: the bias and PReLU-slope gradients
+    int gks() const { return ds ? 1 : ks; }   // the kernel size of the layer's GEMM convs
 };
 
 // the variables the l2 term sums over: the filters, not biases or prelu slopes
@@ -71,6 +85,7 @@ struct TrainState {
     bool wg16 = false;             // ... the exponents and the partial sums of option "train_split16_wgrad"
     unsigned* absmax = nullptr;    // kAbsMaxBlocks partial maxima (launch_texp)
     float *dz = nullptr, *at = nullptr, *part = nullptr, *col = nullptr, *zlast = nullptr, *clip = nullptr;
+    float* dd = nullptr;           // separable layers: the gradient of d (the largest px cin of them)
     float *io_x = nullptr, *io_x2 = nullptr, *io_y = nullptr;
     double *dpart = nullptr, *d_stats = nullptr;
     int w2_blocks = 0;
@@ -93,18 +108,22 @@ static int build_train_plan(dcscn_ctx* h, TrainState* t) {
     const dcscn_config& c = h->cfg;
     float ca = 0.0f;
     const int act = kernel_act(c.activator, &ca);
+    const bool ds = c.depthwise_separable != 0;
     auto add_buf = [&](int stride, int res) { TBuf b; b.stride = stride; b.res = res; t->bufs.push_back(b); return (int)t->bufs.size() - 1; };
     auto add_layer = [&](const std::string& var, const std::string& short_name, int in_buf, int in_off, int cin, int ks, int cout, bool has_act,
-                         int out_buf, int out_off, int ps, int res) -> int {
+                         int out_buf, int out_off, int ps, int res, bool ds) -> int {
         TLayer L;
         L.name = var; L.index = (int)t->layers.size(); L.ks = ks; L.cin = cin; L.cout = cout; L.res = res;
         L.act = has_act ? act : ACT_NONE; L.calpha = has_act ? ca : 0.0f; L.dropout = has_act;
         L.in_buf = in_buf; L.in_off = in_off; L.out_buf = out_buf; L.out_off = out_off; L.ps = ps;
-        L.w_t = tensor_of(h, var + "/conv_W");
+        L.ds = ds;
+        L.w_t = tensor_of(h, var + (ds ? "/pointwise_W" : "/conv_W"));
+        if (ds && (L.dw_t = tensor_of(h, var + "/depthwise_W")) < 0)
+            return fail(h, DCSCN_ERR_UNSUPPORTED, "training: layer %s has no depthwise_W variable", var.c_str());
         L.b_t = tensor_of(h, var + "/conv_B");
         if (has_act && c.activator == DCSCN_ACT_PRELU) L.a_t = tensor_of(h, var + "/prelu/" + short_name + "_prelu");
         if (L.w_t < 0 || (has_act && c.activator == DCSCN_ACT_PRELU && L.a_t < 0))
-            return fail(h, DCSCN_ERR_UNSUPPORTED, "training: layer %s has no conv_W / prelu variable", var.c_str());
+            return fail(h, DCSCN_ERR_UNSUPPORTED, "training: layer %s has no conv_W (pointwise_W) / prelu variable", var.c_str());
         t->layers.push_back(L);
         return DCSCN_OK;
     };
@@ -116,21 +135,21 @@ static int build_train_plan(dcscn_ctx* h, TrainState* t) {
     int in_buf = -1, in_off = 0, cin = c.channels;
     for (int i = 0; i < c.layers; ++i) {
         const std::string nm = "CNN" + std::to_string(i + 1);
-        if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, h->sched[i], true, cat, off[i], 0, 1))) return rc;
+        if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, h->sched[i], true, cat, off[i], 0, 1, ds))) return rc;
         in_buf = cat; in_off = off[i]; cin = h->sched[i];
     }
     if (c.use_nin) {
         const int na = c.nin_filters, nb = c.nin_filters2;
         const int t1 = add_buf(nb, 1), t2 = add_buf(nb + na, 1);
-        if ((rc = add_layer("A1", "A1", cat, 0, total, 1, na, true, t2, nb, 0, 1))) return rc;
-        if ((rc = add_layer("B1", "B1", cat, 0, total, 1, nb, true, t1, 0, 0, 1))) return rc;
-        if ((rc = add_layer("B2", "B2", t1, 0, nb, 3, nb, true, t2, 0, 0, 1))) return rc;           // (3x3 whatever cnn_size); Concat2 = [B2 | A1]
+        if ((rc = add_layer("A1", "A1", cat, 0, total, 1, na, true, t2, nb, 0, 1, ds))) return rc;
+        if ((rc = add_layer("B1", "B1", cat, 0, total, 1, nb, true, t1, 0, 0, 1, ds))) return rc;
+        if ((rc = add_layer("B2", "B2", t1, 0, nb, 3, nb, true, t2, 0, 0, 1, ds))) return rc;       // (3x3 whatever cnn_size); Concat2 = [B2 | A1]
         in_buf = t2; in_off = 0; cin = nb + na;
     } else if (c.legacy_no_c) {
         in_buf = cat; in_off = 0; cin = total;
     } else {
         const int tc = add_buf(c.filters, 1);
-        if ((rc = add_layer("C", "C", cat, 0, total, 1, c.filters, true, tc, 0, 0, 1))) return rc;
+        if ((rc = add_layer("C", "C", cat, 0, total, 1, c.filters, true, tc, 0, 0, 1, ds))) return rc;
         in_buf = tc; in_off = 0; cin = c.filters;
     }
     const int ps_out = c.pixel_shuffler_filters != 0 ? c.pixel_shuffler_filters : cin;
@@ -142,26 +161,29 @@ static int build_train_plan(dcscn_ctx* h, TrainState* t) {
     for (const Stage& st : stages) {
         const int ub = add_buf(st.cout, res * st.s);
         const std::string var = std::string(st.name) + "/" + st.name + "_CNN";
-        if ((rc = add_layer(var, std::string(st.name) + "_CNN", in_buf, in_off, cin, c.cnn_size, st.s * st.s * st.cout, false, ub, 0, st.s, res))) return rc;
+        if ((rc = add_layer(var, std::string(st.name) + "_CNN", in_buf, in_off, cin, c.cnn_size, st.s * st.s * st.cout, false, ub, 0, st.s, res, ds))) return rc;
         in_buf = ub; in_off = 0; cin = st.cout; res *= st.s;
     }
     const int rl = std::max(c.reconstruct_layers, 1);
     for (int i = 0; i < rl - 1; ++i) {
         const std::string nm = "R-CNN" + std::to_string(i + 1);
         const int rb = add_buf(c.reconstruct_filters, res);
-        if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, c.reconstruct_filters, true, rb, 0, 0, res))) return rc;
+        if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, c.reconstruct_filters, true, rb, 0, 0, res, false))) return rc;   // (plain convs even in a separable net, DCSCN.py:313-316)
         in_buf = rb; in_off = 0; cin = c.reconstruct_filters;
     }
     const std::string nm = "R-CNN" + std::to_string(rl);
-    if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, 1, false, -1, 0, 0, res))) return rc;
+    if ((rc = add_layer(nm, nm, in_buf, in_off, cin, c.cnn_size, 1, false, -1, 0, 0, res, ds))) return rc;
     if (t->layers.size() != h->layers.size()) return fail(h, DCSCN_ERR_UNSUPPORTED, "training: internal layer count mismatch");
     return DCSCN_OK;
 }
 
 // wgrad split of a layer: fixed by the shape alone
 static int wgrad_splits(const TLayer& L, int64_t P, int64_t* chunk) {
-    const int64_t tiles = (int64_t)((L.ks * L.ks * L.cin + 31) / 32) * ((L.cout + 31) / 32);
+    const int64_t tiles = (int64_t)((L.gks() * L.gks() * L.cin + 31) / 32) * ((L.cout + 31) / 32);
     int64_t s = std::max<int64_t>(1, std::min<int64_t>((2048 + tiles - 1) / tiles, (P + 1023) / 1024));
+    // a separable layer's pointwise filter is a tile or a few: half the pixels per split, so that twice the workgroups share the k loop, and
+    // at most 256 splits for treduce_wgrad to sum
+    if (L.ds) s = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((2048 + tiles - 1) / tiles, 256), (P + 511) / 512));
     int64_t ch = ((P + s - 1) / s + 15) / 16 * 16;
     s = (P + ch - 1) / ch;
     *chunk = ch;
@@ -178,13 +200,18 @@ static void plan_layer(TLayer& L, int n, int H, int W, bool h16, bool wg16) {
     L.Hr = H * L.res; L.Wr = W * L.res;
     L.px = (int64_t)n * L.Hr * L.Wr;
     L.zcount = L.px * L.cout;
-    L.wcount = (int64_t)L.ks * L.ks * L.cin * L.cout;
-    const bool wide = tconv_h_eligible(L.cin, L.cout);
+    L.wcount = (int64_t)L.gks() * L.gks() * L.cin * L.cout;
+    const bool wide = !L.ds && tconv_h_eligible(L.cin, L.cout);   // separable layers stay on the f32 kernels
     L.h16 = h16 && wide;
     L.wg16 = wg16 && wide;
     if (L.wg16) { L.wp = twgrad_h_plan(L.ks, L.cin, L.cout, n, L.Hr, L.Wr); L.splits = L.wp.splits; }
     else L.splits = wgrad_splits(L, L.px, &L.chunk);
     L.cs = col_splits(L.px, &L.cchunk);
+    if (L.ds) {
+        L.dcount = L.px * L.cin;
+        L.dwcount = (int64_t)L.ks * L.ks * L.cin;
+        L.dws = dw_splits(L.cin, L.px, &L.dcw, &L.dchunk);
+    }
 }
 
 // Walks the arena in its order: every take rounds `words` 4-byte words up to 256 bytes.  Without a base it only sizes; with one it binds
@@ -204,11 +231,12 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
     if (t->arena && t->n == n && t->H == H && t->W == W && t->h16 == h16 && t->wg16 == wg16) return DCSCN_OK;
     // the plan goes into a copy, committed with the new arena: a carve refused for its size leaves the present one as it is
     std::vector<TLayer> layers = t->layers;
-    size_t dz_max = 0, part_max = 0, col_max = 0;
+    size_t dz_max = 0, part_max = 0, col_max = 0, dd_max = 0;
     for (TLayer& L : layers) {
         plan_layer(L, n, H, W, h16, wg16);
         dz_max = std::max(dz_max, (size_t)L.zcount);
-        part_max = std::max(part_max, (size_t)L.splits * L.wcount);
+        part_max = std::max({part_max, (size_t)L.splits * L.wcount, (size_t)L.dws * L.dwcount});
+        dd_max = std::max(dd_max, (size_t)L.dcount);
         col_max = std::max(col_max, (size_t)L.cs * L.cout);
     }
     const size_t P = (size_t)n * H * W, hr = P * h->cfg.scale * h->cfg.scale;
@@ -220,6 +248,8 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
             c.take(b.g, count);
         }
         for (TLayer& L : layers) c.take(L.z, (size_t)L.zcount);
+        for (TLayer& L : layers) c.take(L.d, (size_t)L.dcount, L.ds);
+        c.take(t->dd, dd_max, dd_max > 0);
         c.take(t->dz, dz_max); c.take(t->at, dz_max); c.take(t->part, part_max); c.take(t->col, col_max);
         c.take(t->io_x, P); c.take(t->io_x2, hr); c.take(t->io_y, hr); c.take(t->clip, 4);
         c.take(t->dpart, 2 * (2 * kLossBlocks + (size_t)t->w2_blocks + kNormBlocks) + 16);   // doubles: the partials, then d_stats
@@ -273,9 +303,10 @@ static int launch_layer_conv(dcscn_ctx* h, TrainState* t, const TLayer& L, bool 
         KTRY(h, launch_tconv_gemm_h(a, dgrad ? 1 : 0, st));
         return DCSCN_OK;
     }
-    TConvArgs a{src, src_stride, K, t->n, L.Hr, L.Wr, L.ks, (dgrad ? t->d_wd : t->d_w) + t->off[L.w_t], N, bias, dst, dst_stride};
+    TConvArgs a{src, src_stride, K, t->n, L.Hr, L.Wr, L.gks(), (dgrad ? t->d_wd : t->d_w) + t->off[L.w_t], N, bias, dst, dst_stride};
     dim3 grid((unsigned)((L.px + 127) / 128), (unsigned)((N + 31) / 32));
-    if (dgrad) KTRY(h, hipLaunchKernelGGL(tconv_gemm<1>, grid, dim3(256), 0, st, a));
+    if (dgrad && L.ds) KTRY(h, hipLaunchKernelGGL(tconv_gemm<0>, grid, dim3(256), 0, st, a));   // dd = dz . P^T: written, not accumulated
+    else if (dgrad) KTRY(h, hipLaunchKernelGGL(tconv_gemm<1>, grid, dim3(256), 0, st, a));
     else KTRY(h, hipLaunchKernelGGL(tconv_gemm<0>, grid, dim3(256), 0, st, a));
     return DCSCN_OK;
 }
@@ -321,13 +352,17 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
             KTRY(h, launch_tpack_h(var(L.w_t), L.ks * L.ks, L.cin, L.cout, L.e, L.w16, L.wd16, st));
             continue;
         }
-        KTRY(h, hipLaunchKernelGGL(tpack_dgrad, dim3(grid1(L.wcount)), dim3(256), 0, st, var(L.w_t), L.ks * L.ks, L.cin, L.cout, t->d_wd + t->off[L.w_t]));
+        KTRY(h, hipLaunchKernelGGL(tpack_dgrad, dim3(grid1(L.wcount)), dim3(256), 0, st, var(L.w_t), L.gks() * L.gks(), L.cin, L.cout, t->d_wd + t->off[L.w_t]));
     }
     // ---- forward ----
     for (const TLayer& L : t->layers) {
         float* gdummy;
         const float* in = in_ptr(L, &gdummy);
-        if ((rc = launch_layer_conv(h, t, L, false, in, in_stride(L), L.z, L.cout, st))) return rc;
+        if (L.ds) {   // the depthwise stage into d; the pointwise conv reads d
+            const TDwArgs da{in, in_stride(L), L.cin, n, L.Hr, L.Wr, L.ks, var(L.dw_t)};
+            KTRY(h, hipLaunchKernelGGL(tdw_fwd, dim3(grid1(L.dcount)), dim3(256), 0, st, da, L.d));
+            if ((rc = launch_layer_conv(h, t, L, false, L.d, L.cin, L.z, L.cout, st))) return rc;
+        } else if ((rc = launch_layer_conv(h, t, L, false, in, in_stride(L), L.z, L.cout, st))) return rc;
         if (L.dropout) {
             const TBuf& ob = t->bufs[L.out_buf];
             KTRY(h, hipLaunchKernelGGL(tact_fwd, dim3(grid1(L.zcount)), dim3(256), 0, st, L.z, L.cout, L.px, var(L.a_t), L.calpha, L.act, ob.h + L.out_off,
@@ -368,16 +403,29 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
             const hipError_t we = launch_tconv_wgrad_h(wa, L.wp, st);
             if (we != hipSuccess) return fail(h, DCSCN_ERR_HIP, "tconv_wgrad_h (%s, %zu bytes of LDS): %s", L.name.c_str(), L.wp.lds_bytes, hipGetErrorString(we));
         } else {
-            TWgradArgs wa{in, in_stride(L), L.cin, n, L.Hr, L.Wr, L.ks, t->dz, L.cout, L.chunk, t->part};
-            KTRY(h, hipLaunchKernelGGL(tconv_wgrad, dim3((L.ks * L.ks * L.cin + 31) / 32, (L.cout + 31) / 32, L.splits), dim3(256), 0, st, wa));
+            // (separable: the pointwise filter's, from d)
+            TWgradArgs wa{L.ds ? L.d : in, L.ds ? L.cin : in_stride(L), L.cin, n, L.Hr, L.Wr, L.gks(), t->dz, L.cout, L.chunk, t->part};
+            KTRY(h, hipLaunchKernelGGL(tconv_wgrad, dim3((L.gks() * L.gks() * L.cin + 31) / 32, (L.cout + 31) / 32, L.splits), dim3(256), 0, st, wa));
         }
         KTRY(h, hipLaunchKernelGGL(treduce_wgrad, dim3(grid1(L.wcount)), dim3(256), 0, st, (const float*)t->part, L.splits, L.wcount, (const float*)var(L.w_t),
-                                   (float)tc.l2_decay, t->d_g + t->off[L.w_t]));
+                                   L.ds ? 0.0f : (float)tc.l2_decay, t->d_g + t->off[L.w_t]));
         // bias and PReLU-alpha gradients
         if (L.b_t >= 0 && (rc = launch_col_grad(h, t, L, t->dz, t->d_g + t->off[L.b_t], st))) return rc;
         if (prelu && (rc = launch_col_grad(h, t, L, t->at, t->d_g + t->off[L.a_t], st))) return rc;
         // data gradient, accumulated into the input's gradient (none for the network input)
-        if (gin && (rc = launch_layer_conv(h, t, L, true, t->dz, L.cout, gin, in_stride(L), st))) return rc;
+        if (L.ds) {
+            // dd = dz . P^T, the depthwise filter's gradient from the input and dd (no decay), then the depthwise data gradient into gin
+            if ((rc = launch_layer_conv(h, t, L, true, t->dz, L.cout, t->dd, L.cin, st))) return rc;
+            const TDwArgs wa{in, in_stride(L), L.cin, n, L.Hr, L.Wr, L.ks, var(L.dw_t)};
+            KTRY(h, hipLaunchKernelGGL(tdw_wgrad, dim3(L.ks * L.ks, (L.cin + L.dcw - 1) / L.dcw, L.dws), dim3(256), 0, st, wa, (const float*)t->dd, L.dcw,
+                                       L.dchunk, t->part));
+            KTRY(h, hipLaunchKernelGGL(treduce_wgrad, dim3(grid1(L.dwcount)), dim3(256), 0, st, (const float*)t->part, L.dws, L.dwcount,
+                                       (const float*)var(L.dw_t), 0.0f, t->d_g + t->off[L.dw_t]));
+            if (gin) {
+                const TDwArgs ga{gin, in_stride(L), L.cin, n, L.Hr, L.Wr, L.ks, var(L.dw_t)};
+                KTRY(h, hipLaunchKernelGGL(tdw_dgrad, dim3(grid1(L.dcount)), dim3(256), 0, st, ga, (const float*)t->dd));
+            }
+        } else if (gin && (rc = launch_layer_conv(h, t, L, true, t->dz, L.cout, gin, in_stride(L), st))) return rc;
     }
     // ---- l2 term, global norm, stats ----
     double* w2p = t->dpart + 2 * kLossBlocks;
@@ -526,7 +574,7 @@ int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc) {
     if (!h->finalized) return fail(h, DCSCN_ERR_STATE, "dcscn_train_begin before dcscn_finalize");
     if (h->train) return fail(h, DCSCN_ERR_STATE, "dcscn_train_begin called twice on one handle");
     const dcscn_config& c = h->cfg;
-    if (c.depthwise_separable) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of depthwise separable nets is not implemented");
+    if (c.depthwise_separable && !h->train_separable) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of depthwise separable nets is not implemented");
     if (!c.pixel_shuffler) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of the transposed-conv upsampler (pixel_shuffler = false) is not implemented");
     if (c.batch_norm) return fail(h, DCSCN_ERR_UNSUPPORTED, "batch_norm is not implemented");
     switch (tc->optimizer) {

@@ -402,6 +402,8 @@ class SuperResolution:
         if self._train_engine is not eng:
             if self._data_parallel():
                 self.step = self.train_group.broadcast_object(self.step)   # the dropout key counts steps: rank 0's, when resuming
+            if self.depthwise_separable:
+                eng.set_option("train_separable", 1)             # read by train_begin: without it a separable net is refused
             eng.train_begin(self._train_flags)
             if self.train_split16:
                 eng.set_option("train_split16", 1)

@@ -276,6 +276,9 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * layers, the bias and PReLU-slope gradients, the l2 term and everything else are untouched: only the conv_W gradients of eligible layers
  * (and with them the gradient norm) change bits.  Same parity bars as the default mode; a non-finite operand gives a non-finite result;
  * 0 computes every bit of what a handle that never set the option computes, for either setting of "train_split16".
+ * "train_separable" (default 0; read by dcscn_train_begin alone): with 1, dcscn_train_begin builds the training plan of a
+ * depthwise-separable net instead of refusing it ("Training" below: the semantics and the known departure); with 0 the refusal, its
+ * status and its text are unchanged.  No effect on non-separable configs, and none after dcscn_train_begin.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The
@@ -421,8 +424,8 @@ int64_t dcscn_workspace_bytes(dcscn_handle h);
 int dcscn_num_presplit_tensors(dcscn_handle h);
 
 /* ---------------------------------------------------------------------------------------------------------------------
- * Training (DCSCN.py:334-425, 727-769): f32, non-separable pixel-shuffler nets only; one device per handle, several handles
- * (one per rank) train data-parallel through the record calls below.
+ * Training (DCSCN.py:334-425, 727-769): f32, pixel-shuffler nets only -- the depthwise-separable ones behind option "train_separable"
+ * (below); one device per handle, several handles (one per rank) train data-parallel through the record calls below.
  *
  * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no Winograd, none of the inference split16
  * kernels; option "train_split16" moves the wide layers' forward and data-gradient convs to the f16 matrix pipe at f32 accuracy), with
@@ -437,6 +440,20 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  *   gd:       w <- w - lr g
  *   momentum: a <- mu a + g; w <- w - lr a  (not Nesterov)
  * Everything is deterministic: two identical sequences of calls give bit-identical variables and slots.
+ *
+ * Separable nets (depthwise_separable; option "train_separable", default 0, read by dcscn_train_begin: with 0 such a net is refused, the
+ * option has no effect on a non-separable net and none after dcscn_train_begin).  A separable conv layer (tf.nn.separable_conv2d,
+ * tf_graph.py:155-177) is d = depthwise k x k SAME (in; depthwise_W[k, k, cin, 1]), z = d . pointwise_W[1, 1, cin, cout] + conv_B, then the
+ * activator and dropout as for a plain conv; the dropout layer number is still the layer's index in dcscn_layer_info order, one per
+ * separable layer.  The extra reconstruction layers (R-CNN1 .. R-CNN(rl-1) with reconstruct_layers > 1) are plain convs even in a
+ * separable net.  The trained variables are the handle's tensor list (depthwise_W, pointwise_W, conv_B, the PReLU slopes, conv_W of plain
+ * layers), and the names follow from it: "<var>/depthwise_W/grad", "<var>/pointwise_W/Adam", ...  The l2 term covers conv_W of plain
+ * layers only: the reference sums l2_loss over a list that holds, for a separable layer, the layer's UNUSED conv_W and never depthwise_W or
+ * pointwise_W, so neither gets l2_decay * W in its gradient and neither enters the total loss.
+ * Known departure: the library does not hold those unused conv_W tensors.  Missing are their l2 term in the reference's total loss
+ * (stats[3]) and their l2_decay * |conv_W| in the global norm before clipping (stats[2]).  The gradients and updates of every variable the
+ * library holds are the reference's, unless the clip is active and that term would move the norm.
+ * Options "train_split16" / "train_split16_wgrad" leave separable layers on the f32 kernels; plain layers of a separable net keep their rule.
  *
  * Ties.  At a pre-activation of exactly 0 the derivative of the activator is the one the reference's graph takes
  * (helper/tf_graph.py:82-96) under TensorFlow 1.x's registered gradients:
@@ -491,7 +508,8 @@ typedef struct dcscn_train_config {
 } dcscn_train_config;
 
 /* build_optimizer: after dcscn_finalize; copies the variables to the device master copy and zeroes the slots.
- * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable, pixel_shuffler = 0, batch_norm, adadelta / adagrad / rmsprop. */
+ * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable unless option "train_separable" was set to 1 before this call, pixel_shuffler = 0,
+ * batch_norm, adadelta / adagrad / rmsprop. */
 int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc);
 /* One training step on host buffers (x [n, h, w], x2 and y_true [n, s*h, s*w]); synchronous.  stats (optional, 4 doubles):
  * image_loss, mse, global gradient norm before clipping, total loss (image_loss + the l2 term). */

@@ -8,6 +8,8 @@ with the forward; tact_bwd (the activator and dropout backward) is counted with 
 "train_split16" the eligible layers' convs are tconv_gemm_h<0> (forward) and tconv_gemm_h<1> (dgrad); what the option adds beside
 them -- tabsmax_part, texp_final, tpack_h -- is the phase "scale_pack".  With option "train_split16_wgrad" the eligible layers' weight
 gradients are tconv_wgrad_h<taps> (phase wgrad, like tconv_wgrad), and its exponent reductions count with "scale_pack".  "conv_kernels" lists the conv launches by kernel.
+Separable nets (option "train_separable"): tdw_fwd, tdw_dgrad and tdw_wgrad count with the forward, dgrad and wgrad phases; a separable
+layer's dd = dz . P^T runs on tconv_gemm<0> and so counts with the forward.
 """
 import csv
 import glob
@@ -15,10 +17,10 @@ import json
 import os
 import sys
 
-PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tconv_gemm_hILi1E", "tconv_gemm_h<1>", "tpack_dgrad")),
-          ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tconv_gemm_hILi0E", "tconv_gemm_h<0>", "tact_fwd", "td2s")),
+PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tconv_gemm_hILi1E", "tconv_gemm_h<1>", "tpack_dgrad", "tdw_dgrad")),
+          ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tconv_gemm_hILi0E", "tconv_gemm_h<0>", "tact_fwd", "td2s", "tdw_fwd")),
           ("scale_pack", ("tabsmax_part", "texp_final", "tpack_h")),
-          ("wgrad", ("tconv_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
+          ("wgrad", ("tconv_wgrad", "tdw_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
           ("loss", ("tloss", "tsumsq", "tstats")), ("optimizer", ("topt", "tpowers"))]
 
 

@@ -26,6 +26,12 @@ commit's, in a process of its own.
 sets the second option on the plain run's handle.
 
     python tools/train_bench.py --split16-wgrad
+
+--separable times the depthwise-separable nets (option "train_separable"; L7_x4_DS is BASELINE C5, 20 x 32^2): the HIP step and a torch
+fp32 autograd + Adam step of the same net (a grouped conv2d + a 1x1 conv per separable layer), alternating step by step in ONE process;
+one JSON line per net with both medians and their ratio.  --config L7_x4_DS --no-torch is the profiler run's command.
+
+    python tools/train_bench.py --separable
 """
 import argparse
 import json
@@ -49,7 +55,12 @@ CONFIGS = {
     "L12_x2": dict(),
     "L7_x4": dict(scale=4, layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
                   reconstruct_layers=0, pixel_shuffler_filters=1),
+    "L7_x4_DS": dict(scale=4, layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
+                     reconstruct_layers=0, pixel_shuffler_filters=1, depthwise_separable=True),
+    "L7_x2_DS": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
+                     reconstruct_layers=0, pixel_shuffler_filters=1, depthwise_separable=True),
 }
+SEPARABLE_CASES = (("L7_x4_DS", 20, 32), ("L7_x2_DS", 20, 48))
 LOOP_CASES = (("L7_x2", 20, 48), ("L12_x2", 20, 48), ("L7_x4", 20, 32))
 PEAK_F32_MATRIX = 157.3e12
 
@@ -64,7 +75,8 @@ def step_flops(cfg, n, h, w):
             res *= op["block"]
         if op["op"] != "conv":
             continue
-        macs = n * h * w * res * res * op["k"] * op["k"] * op["cin"] * op["cout"]
+        per_pixel = op["k"] * op["k"] * op["cin"] + op["cin"] * op["cout"] if op["ds"] else op["k"] * op["k"] * op["cin"] * op["cout"]
+        macs = n * h * w * res * res * per_pixel
         total += 2 * macs * (2 if first else 3)
         first = False
     return total
@@ -154,11 +166,19 @@ def bench_split16_wgrad(name, n, size, steps, warmup):
                 ratio_11_over_10=round(med[2] / med[1], 4), ratio_11_over_00=round(med[2] / med[0], 4))
 
 
-def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wgrad=False):
+def hip_engine(cfg):
+    """A training handle on synthetic weights; a separable net gets option "train_separable", which train_begin reads."""
     from dcscn_amd import engine
     eng = engine.Engine(cfg, device=0)
     eng.load_weights(O.synthetic_weights(cfg, seed=0))
+    if cfg["depthwise_separable"]:
+        eng.set_option("train_separable", 1)
     eng.train_begin(flags())
+    return eng
+
+
+def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wgrad=False):
+    eng = hip_engine(cfg)
     if train_split16:
         eng.set_option("train_split16", 1)
     if train_split16_wgrad:
@@ -182,8 +202,9 @@ def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wg
     return float(np.median(times)), float(np.min(times))
 
 
-def bench_torch(cfg, n, h, w, steps, warmup):
-    """The same net as torch fp32 modules on the GPU: autograd + torch.optim.Adam (dropout included)."""
+def torch_step(cfg, n, h, w):
+    """The same net as torch fp32 modules on the GPU: autograd + torch.optim.Adam (dropout included); a separable layer is a grouped
+    conv2d followed by a 1x1 conv.  Returns the function that takes one step."""
     import torch.nn.functional as F
     torch.backends.cudnn.benchmark = True
     dev = torch.device("cuda")
@@ -198,7 +219,11 @@ def bench_torch(cfg, n, h, w, steps, warmup):
         for op in ops:
             if op["op"] == "conv":
                 v = op["var"]
-                z = F.conv2d(t[op["src"]], params[v + "/conv_W"].permute(3, 2, 0, 1), padding=op["k"] // 2)
+                if op["ds"]:
+                    z = F.conv2d(t[op["src"]], params[v + "/depthwise_W"].permute(2, 3, 0, 1), padding=op["k"] // 2, groups=op["cin"])
+                    z = F.conv2d(z, params[v + "/pointwise_W"].permute(3, 2, 0, 1))
+                else:
+                    z = F.conv2d(t[op["src"]], params[v + "/conv_W"].permute(3, 2, 0, 1), padding=op["k"] // 2)
                 if op["bias"]:
                     z = z + params[v + "/conv_B"].view(1, -1, 1, 1)
                 if op["act"] == "prelu":
@@ -218,6 +243,11 @@ def bench_torch(cfg, n, h, w, steps, warmup):
         torch.nn.utils.clip_grad_norm_(list(params.values()), 5.0)
         opt.step()
 
+    return step
+
+
+def bench_torch(cfg, n, h, w, steps, warmup):
+    step = torch_step(cfg, n, h, w)
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -230,6 +260,36 @@ def bench_torch(cfg, n, h, w, steps, warmup):
         b.synchronize()
         times.append(a.elapsed_time(b))
     return float(np.median(times))
+
+
+def bench_separable(name, n, size, steps, warmup):
+    """The HIP step and the torch step of a separable net, alternating step by step in one process, each between events on its stream."""
+    cfg = O.make_config(**CONFIGS[name])
+    eng = hip_engine(cfg)
+    step = torch_step(cfg, n, size, size)
+    x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, size, size))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    times = ([], [])
+    for i in range(warmup + steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, size, size, 1e-4, i, stream=stream.cuda_stream, want_stats=False)
+        b.record(stream)
+        b.synchronize()
+        c, d = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c.record()
+        step()
+        d.record()
+        d.synchronize()
+        if i >= warmup:
+            times[0].append(a.elapsed_time(b))
+            times[1].append(c.elapsed_time(d))
+    eng.close()
+    hip, ref = float(np.median(times[0])), float(np.median(times[1]))
+    return dict(separable_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, hip_ms_per_step=round(hip, 4),
+                torch_ms_per_step=round(ref, 4), hip_over_torch=round(hip / ref, 4),
+                min_ms=[round(float(np.min(times[0])), 4), round(float(np.min(times[1])), 4)])
 
 
 def loop_model(name, n, size, tmp):
@@ -298,6 +358,7 @@ def main():
     ap.add_argument("--split16-wgrad", action="store_true",
                     help="time (train_split16, train_split16_wgrad) = (0, 0), (1, 0), (1, 1) alternating in one process (L12 x2, c-DCSCN x2)")
     ap.add_argument("--train-split16-wgrad", action="store_true", help="set option train_split16_wgrad on the timed handle")
+    ap.add_argument("--separable", action="store_true", help="time the separable nets' HIP step and torch step alternating in one process")
     ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
     if a.library:
@@ -310,6 +371,10 @@ def main():
     if a.split16_wgrad:
         for name in ("L12_x2", "L7_x2"):
             print(json.dumps(bench_split16_wgrad(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
+        return
+    if a.separable:
+        for name, n, size in SEPARABLE_CASES:
+            print(json.dumps(bench_separable(name, n, size, a.steps, a.warmup)), flush=True)
         return
     if a.loop:
         for name, n, size in LOOP_CASES:
