@@ -376,6 +376,10 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->train_separable = value != 0;
         return DCSCN_OK;
     }
+    if (!strcmp(key, "train_transposed")) {         // read by dcscn_train_begin alone: no effect on a pixel-shuffler net, none after it
+        h->train_transposed = value != 0;
+        return DCSCN_OK;
+    }
     if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
         h->p16 = value != 0;
         return DCSCN_OK;

@@ -1,5 +1,5 @@
 // Single-GPU f32 training of the pixel-shuffler DCSCN nets (DCSCN.py:334-425, tf_graph.py:117-177); the depthwise-separable ones behind
-// option "train_separable".
+// option "train_separable", the transposed-conv upsampler (pixel_shuffler = false) behind option "train_transposed".
 //
 // The training plan is its own list of layers over its own arena (TrainState); it shares only the variables with the inference
 // plan.  Every conv runs as one launch of tconv_gemm (implicit GEMM on v_mfma_f32_16x16x4_f32, rows = output pixels, columns =
@@ -16,6 +16,11 @@
 // pixel split, summed by treduce_wgrad), and tdw_dgrad accumulating into the gradient of the layer's input.  Neither filter of a separable
 // layer is in the l2 term (the reference sums l2_loss over the layer's unused conv_W instead): no decay in their gradients.
 //
+// The transposed-conv upsampler Up-TCNN (train_tconv.hpp) takes the place of the Up-PS stages: tup_fwd writes the HR activation buffer
+// (no bias, no activator, no z, no depth_to_space), the gradient of that buffer is the layer's dz as it stands, tup_wgrad + treduce_wgrad
+// give Tconv_W's gradient (with the l2 decay: the reference appends Tconv_W to self.Weights, tf_graph.py:235) and tup_dgrad accumulates
+// into the gradient of the layer's input.  The layer is never separable and never on the split16 kernels.
+//
 // Variables, their gradients and the optimizer slots live in flat f32 buffers in the checkpoint (HWIO) layout, in the order of
 // the graph's variable list (dcscn_tensor_info), so the update is one elementwise launch.
 #include "plan.h"
@@ -23,6 +28,7 @@
 #include "train_wgrad_h.hpp"
 #include "train_kernels.hpp"   // the kernels, and fp contract(off) for them and everything below
 #include "train_dw.hpp"
+#include "train_tconv.hpp"
 
 namespace dcscn_impl {
 
@@ -43,6 +49,8 @@ struct TLayer {
     int w_t = -1, b_t = -1, a_t = -1;
     bool ds = false;               // a separable layer: ks is the depthwise filter's, w_t the pointwise filter [cin][cout], and the convs run with ks = 1 on d
     int dw_t = -1;                 // ... its depthwise filter [ks][ks][cin][1]
+    int up = 0;                    // > 0: the transposed conv Up-TCNN of this stride: ks = 2 up - up % 2, cin = cout, w_t = Tconv_W [ks][ks][oc][ic], res the
+                                   // input's, out_buf the HR activation buffer at res * up; no bias, no activator, no z (train_tconv.hpp)
     float* z = nullptr;            // pre-activation, dense [px, cout]
     float* d = nullptr;            // separable: the depthwise stage's output, dense [px, cin]
     // ---- the launch plan of the current carve: all that the batch shape and the two options fix (plan_layer); run_gradients only reads it ----
@@ -66,7 +74,9 @@ struct TLayer {
 };
 
 // the variables the l2 term sums over: the filters, not biases or prelu slopes
-static bool is_conv_w(const std::string& name) { return name.size() >= 7 && name.compare(name.size() - 7, 7, "/conv_W") == 0; }
+// (Tconv_W as well: tf_graph.py:235 appends it to self.Weights, which DCSCN.py:350 sums)
+static bool ends_with(const std::string& name, const char* tail) { const size_t n = strlen(tail); return name.size() >= n && name.compare(name.size() - n, n, tail) == 0; }
+static bool is_conv_w(const std::string& name) { return ends_with(name, "/conv_W") || ends_with(name, "/Tconv_W"); }
 
 static constexpr int kLossBlocks = 256, kNormBlocks = 256, kW2Blocks = 32;   // (kW2Blocks: per conv_W tensor, for the l2 term)
 
@@ -155,9 +165,20 @@ static int build_train_plan(dcscn_ctx* h, TrainState* t) {
     const int ps_out = c.pixel_shuffler_filters != 0 ? c.pixel_shuffler_filters : cin;
     struct Stage { const char* name; int s; int cout; };
     std::vector<Stage> stages;
-    if (c.scale == 4) { stages.push_back({"Up-PS", 2, cin}); stages.push_back({"Up-PS2", 2, ps_out}); }
-    else stages.push_back({"Up-PS", c.scale, ps_out});
+    if (c.pixel_shuffler) {   // (else: no stages, Up-TCNN below)
+        if (c.scale == 4) { stages.push_back({"Up-PS", 2, cin}); stages.push_back({"Up-PS2", 2, ps_out}); }
+        else stages.push_back({"Up-PS", c.scale, ps_out});
+    }
     int res = 1;
+    if (!c.pixel_shuffler) {
+        // build_transposed_conv("Up-TCNN", H[-1], scale, channels): one stage for any scale, C -> C, in place of the Up-PS stages
+        TLayer L;
+        L.name = "Up-TCNN"; L.index = (int)t->layers.size(); L.up = c.scale; L.ks = 2 * c.scale - c.scale % 2; L.cin = L.cout = cin; L.res = res;
+        L.in_buf = in_buf; L.in_off = in_off; L.out_buf = add_buf(cin, res * c.scale);
+        if ((L.w_t = tensor_of(h, "Up-TCNN/Tconv_W")) < 0) return fail(h, DCSCN_ERR_UNSUPPORTED, "training: layer Up-TCNN has no Tconv_W variable");
+        t->layers.push_back(L);
+        in_buf = L.out_buf; in_off = 0; res *= c.scale;
+    }
     for (const Stage& st : stages) {
         const int ub = add_buf(st.cout, res * st.s);
         const std::string var = std::string(st.name) + "/" + st.name + "_CNN";
@@ -199,9 +220,9 @@ static int col_splits(int64_t P, int64_t* chunk) {
 static void plan_layer(TLayer& L, int n, int H, int W, bool h16, bool wg16) {
     L.Hr = H * L.res; L.Wr = W * L.res;
     L.px = (int64_t)n * L.Hr * L.Wr;
-    L.zcount = L.px * L.cout;
+    L.zcount = L.up > 0 ? 0 : L.px * L.cout;                      // (Up-TCNN writes its output buffer: no z)
     L.wcount = (int64_t)L.gks() * L.gks() * L.cin * L.cout;
-    const bool wide = !L.ds && tconv_h_eligible(L.cin, L.cout);   // separable layers stay on the f32 kernels
+    const bool wide = !L.ds && L.up == 0 && tconv_h_eligible(L.cin, L.cout);   // separable layers and Up-TCNN stay on the f32 kernels
     L.h16 = h16 && wide;
     L.wg16 = wg16 && wide;
     if (L.wg16) { L.wp = twgrad_h_plan(L.ks, L.cin, L.cout, n, L.Hr, L.Wr); L.splits = L.wp.splits; }
@@ -247,7 +268,7 @@ static int carve(dcscn_ctx* h, TrainState* t, int n, int H, int W) {
             c.take(b.h, count);
             c.take(b.g, count);
         }
-        for (TLayer& L : layers) c.take(L.z, (size_t)L.zcount);
+        for (TLayer& L : layers) c.take(L.z, (size_t)L.zcount, L.zcount > 0);
         for (TLayer& L : layers) c.take(L.d, (size_t)L.dcount, L.ds);
         c.take(t->dd, dd_max, dd_max > 0);
         c.take(t->dz, dz_max); c.take(t->at, dz_max); c.take(t->part, part_max); c.take(t->col, col_max);
@@ -358,6 +379,11 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
     for (const TLayer& L : t->layers) {
         float* gdummy;
         const float* in = in_ptr(L, &gdummy);
+        if (L.up > 0) {   // Up-TCNN: one GEMM per output phase, straight into the HR activation buffer
+            const TUpArgs ua{const_cast<float*>(in), in_stride(L), L.cin, n, L.Hr, L.Wr, L.up, L.ks, t->d_wd + t->off[L.w_t], t->bufs[L.out_buf].h, 0, nullptr};
+            KTRY(h, hipLaunchKernelGGL(tup_fwd, dim3((unsigned)((L.px + 127) / 128), (L.cout + 31) / 32, L.up * L.up), dim3(256), 0, st, ua));
+            continue;
+        }
         if (L.ds) {   // the depthwise stage into d; the pointwise conv reads d
             const TDwArgs da{in, in_stride(L), L.cin, n, L.Hr, L.Wr, L.ks, var(L.dw_t)};
             KTRY(h, hipLaunchKernelGGL(tdw_fwd, dim3(grid1(L.dcount)), dim3(256), 0, st, da, L.d));
@@ -384,6 +410,17 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
         float* gin;
         const float* in = in_ptr(L, &gin);
         const bool prelu = L.a_t >= 0;
+        if (L.up > 0) {
+            // Up-TCNN: dz is the gradient of its output buffer as it stands; Tconv_W's gradient (+ l2_decay * W), then the data gradient
+            float* dout = t->bufs[L.out_buf].g;
+            const TUpArgs wa{const_cast<float*>(in), in_stride(L), L.cin, n, L.Hr, L.Wr, L.up, L.ks, nullptr, dout, L.chunk, t->part};
+            KTRY(h, hipLaunchKernelGGL(tup_wgrad, dim3((L.ks * L.ks * L.cout + 31) / 32, (L.cin + 31) / 32, L.splits), dim3(256), 0, st, wa));
+            KTRY(h, hipLaunchKernelGGL(treduce_wgrad, dim3(grid1(L.wcount)), dim3(256), 0, st, (const float*)t->part, L.splits, L.wcount, (const float*)var(L.w_t),
+                                       (float)tc.l2_decay, t->d_g + t->off[L.w_t]));
+            const TUpArgs ga{gin, in_stride(L), L.cin, n, L.Hr, L.Wr, L.up, L.ks, var(L.w_t), dout, 0, nullptr};
+            KTRY(h, hipLaunchKernelGGL(tup_dgrad, dim3((unsigned)((L.px + 127) / 128), (L.cin + 31) / 32), dim3(256), 0, st, ga));
+            continue;
+        }
         if (L.dropout) {
             const TBuf& ob = t->bufs[L.out_buf];
             KTRY(h, hipLaunchKernelGGL(tact_bwd, dim3(grid1(L.zcount)), dim3(256), 0, st, (const float*)(ob.g + L.out_off), ob.stride, (const float*)L.z, L.cout,
@@ -575,7 +612,7 @@ int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc) {
     if (h->train) return fail(h, DCSCN_ERR_STATE, "dcscn_train_begin called twice on one handle");
     const dcscn_config& c = h->cfg;
     if (c.depthwise_separable && !h->train_separable) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of depthwise separable nets is not implemented");
-    if (!c.pixel_shuffler) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of the transposed-conv upsampler (pixel_shuffler = false) is not implemented");
+    if (!c.pixel_shuffler && !h->train_transposed) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of the transposed-conv upsampler (pixel_shuffler = false) is not implemented");
     if (c.batch_norm) return fail(h, DCSCN_ERR_UNSUPPORTED, "batch_norm is not implemented");
     switch (tc->optimizer) {
         case DCSCN_OPTIMIZER_ADAM: case DCSCN_OPTIMIZER_GD: case DCSCN_OPTIMIZER_MOMENTUM: break;

@@ -29,6 +29,19 @@ from . import ckpt, engine, frozen, imaging as util, shard
 BICUBIC_METHOD_STRING = "bicubic"
 
 
+def transposed_conv_initial(scale, channels):
+    """The initial value of ``Up-TCNN/Tconv_W`` (utilty.py:366-390): shape [k, k, channels, channels] with k = 2 scale - scale % 2, zero
+    everywhere except ``W[:, :, i, i]`` = the bilinear upsampling filter of size k.  Pure numpy: needs neither the library nor a GPU."""
+    k = 2 * scale - scale % 2
+    factor = (k + 1) // 2
+    center = factor - 1 if k % 2 == 1 else factor - 0.5
+    row = 1 - np.abs(np.arange(k) - center) / factor
+    w = np.zeros((k, k, channels, channels), np.float32)
+    for i in range(channels):
+        w[:, :, i, i] = np.outer(row, row)
+    return w
+
+
 def build_input_image(image, width=0, height=0, channels=1, scale=1, alignment=0, convert_ycbcr=True):
     """Crop / align / convert / downscale a loaded image into the network input (loader.py:42-67)."""
     if width != 0 and height != 0:
@@ -261,7 +274,7 @@ class SuperResolution:
 
     def init_all_variables(self):
         """``tf.global_variables_initializer`` (tf_graph.py:73-75): He truncated-normal filters
-        (utilty.py:360-363), zero bias, PReLU slope 0.1 -- replaced by ``load_model`` for real use."""
+        (utilty.py:360-363), zero bias, PReLU slope 0.1, the bilinear Tconv_W of a transposed-conv net -- replaced by ``load_model`` for real use."""
         if self._engine is None:
             self.build_graph()
         rng = np.random.default_rng()
@@ -273,6 +286,8 @@ class SuperResolution:
                 tensors[name] = np.clip(rng.standard_normal(shape), -2.0, 2.0).astype(np.float32) * np.float32(std)
             elif leaf == "conv_B":
                 tensors[name] = np.zeros(shape, np.float32)
+            elif leaf == "Tconv_W":
+                tensors[name] = transposed_conv_initial(self.scale, shape[2])
             else:
                 tensors[name] = np.full(shape, 0.1, np.float32)
         if self._data_parallel():
@@ -404,6 +419,8 @@ class SuperResolution:
                 self.step = self.train_group.broadcast_object(self.step)   # the dropout key counts steps: rank 0's, when resuming
             if self.depthwise_separable:
                 eng.set_option("train_separable", 1)             # read by train_begin: without it a separable net is refused
+            if not self.pixel_shuffler:
+                eng.set_option("train_transposed", 1)            # likewise for the transposed-conv upsampler
             eng.train_begin(self._train_flags)
             if self.train_split16:
                 eng.set_option("train_split16", 1)

@@ -279,6 +279,10 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * "train_separable" (default 0; read by dcscn_train_begin alone): with 1, dcscn_train_begin builds the training plan of a
  * depthwise-separable net instead of refusing it ("Training" below: the semantics and the known departure); with 0 the refusal, its
  * status and its text are unchanged.  No effect on non-separable configs, and none after dcscn_train_begin.
+ * "train_transposed" (default 0; read by dcscn_train_begin alone): with 1, dcscn_train_begin builds the training plan of a net with the
+ * transposed-conv upsampler (pixel_shuffler = 0, layer Up-TCNN) instead of refusing it ("Training" below); with 0 the refusal, its status
+ * and its text are unchanged.  No effect on pixel-shuffler configs, and none after dcscn_train_begin.  A net that is both separable and
+ * transposed needs this option and "train_separable"; with one of them set the refusal names the other.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The
@@ -424,15 +428,15 @@ int64_t dcscn_workspace_bytes(dcscn_handle h);
 int dcscn_num_presplit_tensors(dcscn_handle h);
 
 /* ---------------------------------------------------------------------------------------------------------------------
- * Training (DCSCN.py:334-425, 727-769): f32, pixel-shuffler nets only -- the depthwise-separable ones behind option "train_separable"
- * (below); one device per handle, several handles (one per rank) train data-parallel through the record calls below.
+ * Training (DCSCN.py:334-425, 727-769): f32; the depthwise-separable nets behind option "train_separable" and the transposed-conv
+ * upsampler (pixel_shuffler = 0) behind option "train_transposed" (both below); one device per handle, several handles (one per rank) train data-parallel through the record calls below.
  *
  * Forward in training mode = the inference graph run layer by layer in f32 (no tail fold, no Winograd, none of the inference split16
  * kernels; option "train_split16" moves the wide layers' forward and data-gradient convs to the f16 matrix pipe at f32 accuracy), with
  * dropout after the activator of every conv that has one (CNN1..L, A1, B1, B2, C, the non-final R-CNN layers; not the Up-PS
- * convs, not the last R-CNN): out = h / keep where the mask is 1, else 0.
+ * convs or Up-TCNN, not the last R-CNN): out = h / keep where the mask is 1, else 0.
  * Loss: diff = (R-CNN_last + x2) - y_true over the whole HR patch; mse = mean(diff^2); image_loss = mse, or mean(|diff|) with
- * use_l1_loss; loss = image_loss + l2_decay * sum over every conv_W of 0.5 * ||W||^2 (biases and PReLU alphas not decayed).
+ * use_l1_loss; loss = image_loss + l2_decay * sum over every conv_W (and Up-TCNN's Tconv_W) of 0.5 * ||W||^2 (biases and PReLU alphas not decayed).
  * Gradients of `loss` for every variable; clipping (clipping_norm > 0): g <- g * c / max(||g||_global, c) over all variables;
  * then TF's update rule:
  *   adam:     lr_t = lr * sqrt(1 - beta2_power) / (1 - beta1_power); m <- b1 m + (1 - b1) g; v <- b2 v + (1 - b2) g^2;
@@ -454,6 +458,19 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  * (stats[3]) and their l2_decay * |conv_W| in the global norm before clipping (stats[2]).  The gradients and updates of every variable the
  * library holds are the reference's, unless the clip is active and that term would move the norm.
  * Options "train_split16" / "train_split16_wgrad" leave separable layers on the f32 kernels; plain layers of a separable net keep their rule.
+ *
+ * Transposed-conv nets (pixel_shuffler = 0; option "train_transposed", default 0, read by dcscn_train_begin: with 0 such a net is refused,
+ * the option has no effect on a pixel-shuffler net and none after dcscn_train_begin).  Layer Up-TCNN (build_transposed_conv,
+ * tf_graph.py:219-236) takes the place of the Up-PS stages, one stage for any scale s: out = tf.nn.conv2d_transpose(in,
+ * Tconv_W[k, k, out C, in C], stride s, SAME) with k = 2 s - s % 2 and C -> C channels, no bias, no activator and no dropout of its own.  It
+ * runs as itself, k^2 C^2 multiply-adds per LR pixel in each of forward, data gradient and weight gradient, not as the derived 3x3 filter of
+ * the inference plan.  Up-TCNN/Tconv_W is one more variable of the tensor list ("Up-TCNN/Tconv_W/grad", ".../Adam", ".../Adam_1",
+ * ".../Momentum", the records of the data-parallel calls).  It IS in the l2 term (the reference appends it to its weight list,
+ * tf_graph.py:235): l2_decay * W in its gradient, 0.5 ||W||^2 in the total loss.  A layer's dropout number stays its index in
+ * dcscn_layer_info order, so Up-TCNN takes a number although it has no dropout: the layers behind it (R-CNN1 .. with reconstruct_layers > 1)
+ * are numbered as dcscn_layer_info numbers them.  Options "train_split16" / "train_split16_wgrad" leave Up-TCNN on its f32 kernels; the other
+ * layers of such a net take them as before.  A net that is also separable needs "train_separable" as well (Up-TCNN itself is never
+ * separable).  After a step the inference plan's derived filter is rebuilt from the trained Tconv_W like every other packed filter.
  *
  * Ties.  At a pre-activation of exactly 0 the derivative of the activator is the one the reference's graph takes
  * (helper/tf_graph.py:82-96) under TensorFlow 1.x's registered gradients:
@@ -508,8 +525,8 @@ typedef struct dcscn_train_config {
 } dcscn_train_config;
 
 /* build_optimizer: after dcscn_finalize; copies the variables to the device master copy and zeroes the slots.
- * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable unless option "train_separable" was set to 1 before this call, pixel_shuffler = 0,
- * batch_norm, adadelta / adagrad / rmsprop. */
+ * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable unless option "train_separable" was set to 1 before this call, pixel_shuffler = 0
+ * unless option "train_transposed" was, batch_norm, adadelta / adagrad / rmsprop. */
 int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc);
 /* One training step on host buffers (x [n, h, w], x2 and y_true [n, s*h, s*w]); synchronous.  stats (optional, 4 doubles):
  * image_loss, mse, global gradient norm before clipping, total loss (image_loss + the l2 term). */

@@ -10,6 +10,8 @@ them -- tabsmax_part, texp_final, tpack_h -- is the phase "scale_pack".  With op
 gradients are tconv_wgrad_h<taps> (phase wgrad, like tconv_wgrad), and its exponent reductions count with "scale_pack".  "conv_kernels" lists the conv launches by kernel.
 Separable nets (option "train_separable"): tdw_fwd, tdw_dgrad and tdw_wgrad count with the forward, dgrad and wgrad phases; a separable
 layer's dd = dz . P^T runs on tconv_gemm<0> and so counts with the forward.
+Transposed-conv nets (option "train_transposed"): tup_fwd, tup_dgrad and tup_wgrad (layer Up-TCNN) count with the forward, dgrad and wgrad
+phases and are listed with the conv launches.
 """
 import csv
 import glob
@@ -17,10 +19,10 @@ import json
 import os
 import sys
 
-PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tconv_gemm_hILi1E", "tconv_gemm_h<1>", "tpack_dgrad", "tdw_dgrad")),
-          ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tconv_gemm_hILi0E", "tconv_gemm_h<0>", "tact_fwd", "td2s", "tdw_fwd")),
+PHASES = [("dgrad", ("tconv_gemmILi1E", "tconv_gemm<1>", "tconv_gemm_hILi1E", "tconv_gemm_h<1>", "tpack_dgrad", "tdw_dgrad", "tup_dgrad")),
+          ("forward", ("tconv_gemmILi0E", "tconv_gemm<0>", "tconv_gemm_hILi0E", "tconv_gemm_h<0>", "tact_fwd", "td2s", "tdw_fwd", "tup_fwd")),
           ("scale_pack", ("tabsmax_part", "texp_final", "tpack_h")),
-          ("wgrad", ("tconv_wgrad", "tdw_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
+          ("wgrad", ("tconv_wgrad", "tdw_wgrad", "tup_wgrad", "treduce_wgrad", "tcol_partial", "tcol_final", "tact_bwd")),
           ("loss", ("tloss", "tsumsq", "tstats")), ("optimizer", ("topt", "tpowers"))]
 
 
@@ -36,7 +38,7 @@ def main():
         with open(f) as fh:
             for row in csv.DictReader(fh):
                 name, total_ns = row["Name"], float(row["TotalDurationNs"])
-                if "tconv_" in name:
+                if "tconv_" in name or "tup_" in name:
                     convs[name] = round(convs.get(name, 0.0) + total_ns / 1e6 / steps, 4)
                 for phase, keys in PHASES:
                     if any(k in name for k in keys):

@@ -32,6 +32,12 @@ fp32 autograd + Adam step of the same net (a grouped conv2d + a 1x1 conv per sep
 one JSON line per net with both medians and their ratio.  --config L7_x4_DS --no-torch is the profiler run's command.
 
     python tools/train_bench.py --separable
+
+--transposed does the same for the transposed-conv nets (--pixel_shuffler=false, option "train_transposed"): L12_x2_T is the reference's
+defaults with pixel_shuffler = false (its README's training command line), L7_x2_T the c-DCSCN x2 topology, both at 20 x 48^2.
+--config L7_x2_T --no-torch is the profiler run's command (its pixel-shuffler twin at the same shape: --config L7_x2_PS32; L12_x2_T's is L12_x2).
+
+    python tools/train_bench.py --transposed
 """
 import argparse
 import json
@@ -59,7 +65,13 @@ CONFIGS = {
                      reconstruct_layers=0, pixel_shuffler_filters=1, depthwise_separable=True),
     "L7_x2_DS": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
                      reconstruct_layers=0, pixel_shuffler_filters=1, depthwise_separable=True),
+    # the pixel-shuffler twin of L7_x2_T at the same shape: Up-PS from 32 to 4 x 32 channels (L7_x2's has pixel_shuffler_filters = 1)
+    "L7_x2_PS32": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8, reconstruct_layers=0),
+    "L12_x2_T": dict(pixel_shuffler=False),
+    "L7_x2_T": dict(layers=7, filters=32, min_filters=8, filters_decay_gamma=1.2, nin_filters=24, nin_filters2=8,
+                    reconstruct_layers=0, pixel_shuffler=False),
 }
+TRANSPOSED_CASES = (("L12_x2_T", 20, 48), ("L7_x2_T", 20, 48))
 SEPARABLE_CASES = (("L7_x4_DS", 20, 32), ("L7_x2_DS", 20, 48))
 LOOP_CASES = (("L7_x2", 20, 48), ("L12_x2", 20, 48), ("L7_x4", 20, 32))
 PEAK_F32_MATRIX = 157.3e12
@@ -73,6 +85,10 @@ def step_flops(cfg, n, h, w):
     for op in O.build_topology(cfg):
         if op["op"] == "depth_to_space":
             res *= op["block"]
+        if op["op"] == "conv_transpose":      # k^2 C^2 MACs per input pixel in each of the three directions
+            k = 2 * op["scale"] - op["scale"] % 2
+            total += 2 * n * h * w * res * res * k * k * op["channels"] ** 2 * 3
+            res *= op["scale"]
         if op["op"] != "conv":
             continue
         per_pixel = op["k"] * op["k"] * op["cin"] + op["cin"] * op["cout"] if op["ds"] else op["k"] * op["k"] * op["cin"] * op["cout"]
@@ -167,12 +183,15 @@ def bench_split16_wgrad(name, n, size, steps, warmup):
 
 
 def hip_engine(cfg):
-    """A training handle on synthetic weights; a separable net gets option "train_separable", which train_begin reads."""
+    """A training handle on synthetic weights; a separable net gets option "train_separable" and a transposed-conv net option
+    "train_transposed", which train_begin reads."""
     from dcscn_amd import engine
     eng = engine.Engine(cfg, device=0)
     eng.load_weights(O.synthetic_weights(cfg, seed=0))
     if cfg["depthwise_separable"]:
         eng.set_option("train_separable", 1)
+    if not cfg["pixel_shuffler"]:
+        eng.set_option("train_transposed", 1)
     eng.train_begin(flags())
     return eng
 
@@ -209,7 +228,7 @@ def torch_step(cfg, n, h, w):
     torch.backends.cudnn.benchmark = True
     dev = torch.device("cuda")
     params = {k: torch.tensor(v, device=dev, requires_grad=True) for k, v in O.synthetic_weights(cfg, seed=0).items()}
-    conv_w = {k: v for k, v in params.items() if k.endswith("/conv_W")}
+    conv_w = {k: v for k, v in params.items() if k.endswith(("/conv_W", "/Tconv_W"))}
     opt = torch.optim.Adam(params.values(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8)
     x, x2, y = (torch.from_numpy(a).to(dev).permute(0, 3, 1, 2).contiguous() for a in batch(cfg, n, h, w))
     ops = O.build_topology(cfg)
@@ -235,6 +254,9 @@ def torch_step(cfg, n, h, w):
                 t[op["dst"]] = torch.cat([t[s] for s in op["srcs"]], 1)
             elif op["op"] == "depth_to_space":
                 t[op["dst"]] = F.pixel_shuffle(t[op["src"]], op["block"])
+            elif op["op"] == "conv_transpose":
+                wt, sc = params[op["var"] + "/Tconv_W"], op["scale"]
+                t[op["dst"]] = F.conv_transpose2d(t[op["src"]], wt.permute(3, 2, 0, 1), stride=sc, padding=(wt.shape[0] - sc) // 2)
             elif op["op"] == "add":
                 t[op["dst"]] = t[op["srcs"][0]] + t[op["srcs"][1]]
         loss = F.mse_loss(t["y_"], y) + 1e-4 * sum(0.5 * (wt * wt).sum() for wt in conv_w.values())
@@ -263,7 +285,7 @@ def bench_torch(cfg, n, h, w, steps, warmup):
 
 
 def bench_separable(name, n, size, steps, warmup):
-    """The HIP step and the torch step of a separable net, alternating step by step in one process, each between events on its stream."""
+    """The HIP step and the torch step of a separable (or transposed-conv) net, alternating step by step in one process, each between events on its stream."""
     cfg = O.make_config(**CONFIGS[name])
     eng = hip_engine(cfg)
     step = torch_step(cfg, n, size, size)
@@ -287,7 +309,7 @@ def bench_separable(name, n, size, steps, warmup):
             times[1].append(c.elapsed_time(d))
     eng.close()
     hip, ref = float(np.median(times[0])), float(np.median(times[1]))
-    return dict(separable_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, hip_ms_per_step=round(hip, 4),
+    return dict([("separable_compare" if cfg["depthwise_separable"] else "transposed_compare", name)], batch=n, lr_size=size, steps=steps, warmup=warmup, hip_ms_per_step=round(hip, 4),
                 torch_ms_per_step=round(ref, 4), hip_over_torch=round(hip / ref, 4),
                 min_ms=[round(float(np.min(times[0])), 4), round(float(np.min(times[1])), 4)])
 
@@ -359,6 +381,7 @@ def main():
                     help="time (train_split16, train_split16_wgrad) = (0, 0), (1, 0), (1, 1) alternating in one process (L12 x2, c-DCSCN x2)")
     ap.add_argument("--train-split16-wgrad", action="store_true", help="set option train_split16_wgrad on the timed handle")
     ap.add_argument("--separable", action="store_true", help="time the separable nets' HIP step and torch step alternating in one process")
+    ap.add_argument("--transposed", action="store_true", help="time the transposed-conv nets' HIP step and torch step alternating in one process")
     ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
     if a.library:
@@ -372,8 +395,8 @@ def main():
         for name in ("L12_x2", "L7_x2"):
             print(json.dumps(bench_split16_wgrad(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
         return
-    if a.separable:
-        for name, n, size in SEPARABLE_CASES:
+    if a.separable or a.transposed:
+        for name, n, size in (SEPARABLE_CASES if a.separable else TRANSPOSED_CASES):
             print(json.dumps(bench_separable(name, n, size, a.steps, a.warmup)), flush=True)
         return
     if a.loop:
