@@ -86,8 +86,9 @@ def _assert_same_bits(a, b):
 class Rig:
     """`world` handles on device 0, one stream, one [world, record_floats] tensor of records."""
 
-    def __init__(self, name, splits, **flags):
-        self.engines = [_engine(name, **flags) for _ in splits]
+    def __init__(self, name, splits, make=None, **flags):
+        """`make(name, **flags)` opens a rank's handle: _engine by default, another net's for tests/test_train_variants_surface_hip.py."""
+        self.engines = [(make or _engine)(name, **flags) for _ in splits]
         self.bounds = np.concatenate([[0], np.cumsum(splits)])
         self.stream = torch.cuda.Stream()
         self.records = torch.zeros((len(splits), self.engines[0].train_record_floats()), dtype=torch.float32, device="cuda")
@@ -152,7 +153,12 @@ def _check_parity(name, splits, keep, l1):
         rig.local(_device(_batch(name)), KEY)
         stats = rig.apply(1e-3, which=[0])[0]
         got = {k: rig.engines[0].get_tensor(k + "/grad") for k in weights}
-    print("%s %s keep %g l1 %d: stats %r, reference %r norm %r" % (name, splits, keep, l1, stats, ref, norm))
+    _assert_parity("%s %s keep %g l1 %d" % (name, splits, keep, l1), ref, g64, norm, stats, got)
+
+
+def _assert_parity(label, ref, g64, norm, stats, got):
+    """The reduced gradient and the stats of rank 0 against the float64 reference of the whole batch."""
+    print("%s: stats %r, reference %r norm %r" % (label, stats, ref, norm))
     for k, g in g64.items():
         err, top = float(np.max(np.abs(got[k].astype(np.float64) - g))), float(np.max(np.abs(g)))
         print("  %-40s max err %.3g  bound %.3g" % (k, err, 1e-4 * top))

@@ -34,12 +34,13 @@ def _worst(ratios):
     return ratios[name], name
 
 
-def _compare(label, cfg, weights, x, x2, y, stats, got, keep=1.0, key=0, l1=False, tol=1e-4, context=None):
+def _compare(label, cfg, weights, x, x2, y, stats, got, keep=1.0, key=0, l1=False, tol=1e-4, context=None, restatement=R):
     """The assertions of the random walk: gradients within ``tol * max|g64|``, exact zeros where the float64 gradient is
     identically zero, image loss / mse / total loss to 1e-6 relative, the global norm to 1e-4 relative, everything finite.
-    Returns (device ratio, float32 torch ratio)."""
-    ref, g64 = R.loss_and_grads(cfg, weights, x, x2, y, keep=keep, key=key, l1=l1, l2_decay=L2_DECAY)
-    _, g32 = R.loss_and_grads(cfg, {k: v.astype(np.float32) for k, v in weights.items()}, x, x2, y, keep=keep, key=key, l1=l1,
+    ``restatement`` is the module whose ``loss_and_grads`` restates the net's graph (tests/train_ref.py; train_ref_transposed.py for
+    the separable and the transposed nets).  Returns (device ratio, float32 torch ratio)."""
+    ref, g64 = restatement.loss_and_grads(cfg, weights, x, x2, y, keep=keep, key=key, l1=l1, l2_decay=L2_DECAY)
+    _, g32 = restatement.loss_and_grads(cfg, {k: v.astype(np.float32) for k, v in weights.items()}, x, x2, y, keep=keep, key=key, l1=l1,
                               l2_decay=L2_DECAY, dtype=torch.float32)
     _, norm = R.clip_factor(g64, 0.0)
     dev, f32 = _ratios(got, g64), _ratios(g32, g64)

@@ -64,6 +64,20 @@ def dw_splits(cin, pixels):
     return (pixels + chunk - 1) // chunk, chunk
 
 
+def wgrad_splits(ks, cin, cout, pixels, ds=False):
+    """(splits, pixels per split) of a GEMM layer's weight gradient (train.hip: wgrad_splits), fixed by the shape alone.  ``ks`` is the
+    kernel size of the GEMM: 1 for a separable layer's pointwise filter (``ds``), k = 2 s - s % 2 with cin = cout = C for Up-TCNN, whose
+    pixels are the LR ones."""
+    tiles = ((ks * ks * cin + 31) // 32) * ((cout + 31) // 32)
+    by_tiles = (2048 + tiles - 1) // tiles
+    if ds:
+        s = max(1, min(by_tiles, 256, (pixels + 511) // 512))
+    else:
+        s = max(1, min(by_tiles, (pixels + 1023) // 1024))
+    chunk = ((pixels + s - 1) // s + 15) // 16 * 16
+    return (pixels + chunk - 1) // chunk, chunk
+
+
 def forward(cfg, leaves, x, x2, keep=1.0, key=0, dtype=torch.float64):
     """y_ of the training graph (torch, NCHW) from ``leaves`` {name: tensor}; x, x2 numpy NHWC."""
     t = {"x": torch.from_numpy(np.asarray(x, np.float64)).to(dtype).permute(0, 3, 1, 2),
