@@ -43,7 +43,7 @@ SOURCE_TABLE = {
     "conv5_h_fast16.hip": (KERNEL, True), "feat_stream_redo.hip": (NO_SLP, False), "feat3_stream.hip": (KERNEL, True),
     "feat3_stream_fast16.hip": (KERNEL, True), "feat_stream_fast16.hip": (KERNEL, True),
     "train.hip": (REMARKS, True), "train_data.hip": ([], False), "train_h.hip": (KERNEL, True),
-    "train_wgrad_h.hip": (KERNEL, True),
+    "train_wgrad_h.hip": (KERNEL, True), "summary.hip": (NO_CONTRACT, False),
 }
 SOURCES = list(SOURCE_TABLE)
 EXTRA_FLAGS = {src: flags for src, (flags, _) in SOURCE_TABLE.items()}

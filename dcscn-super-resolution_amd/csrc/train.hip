@@ -29,6 +29,7 @@
 #include "train_kernels.hpp"   // the kernels, and fp contract(off) for them and everything below
 #include "train_dw.hpp"
 #include "train_tconv.hpp"
+#include "summary.hpp"
 
 namespace dcscn_impl {
 
@@ -104,6 +105,14 @@ struct TrainState {
     // dcscn_train_apply_records: [kNormBlocks] norm partials | 4 stats | clip (float) | ok (int) | [world] rank weights, as doubles
     double* d_red = nullptr; size_t red_cap = 0;
     hipEvent_t join_ev = nullptr;  // join_stream's event, made on first use
+    // dcscn_train_log_pass (the end of this file): the summarised tensors by name, their records as the last pass left them on the host
+    // ([names] dcscn_summary | [names][kSummaryBuckets] int64), and the device buffer they are reduced into (the same, then the scratch)
+    std::vector<std::string> sum_names;
+    std::map<std::string, int> sum_index;
+    std::vector<char> sum_host;
+    char* sum_dev = nullptr; size_t sum_cap = 0;
+    bool sum_valid = false;        // a log pass has filled sum_host
+    bool acts_valid = false;       // the arena holds that pass's activations and y_ (in `at`): until the next prepare_step
 };
 
 static int grid1(int64_t n) { return (int)((n + 255) / 256); }
@@ -346,12 +355,13 @@ static int launch_grad_norm(dcscn_ctx* h, TrainState* t, double* g2p, hipStream_
 }
 
 // forward + backward of one step (gradients into d_g, stats into d_stats); no host synchronisation
+// (dropout_on = false: the log pass, which runs the graph with dropout = 1.0 whatever keep_prob the handle trains with)
 static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const float* x2, const float* yt, uint64_t key, hipStream_t st,
-                         int64_t first_index = 0) {
+                         int64_t first_index = 0, bool dropout_on = true) {
     const dcscn_train_config& tc = t->tc;
     const int n = t->n;
     const int64_t P = (int64_t)n * t->H * t->W;
-    const bool drop = tc.keep_prob < 1.0;
+    const bool drop = dropout_on && tc.keep_prob < 1.0;
     const float keep = (float)tc.keep_prob;
     const uint32_t thresh = drop ? (uint32_t)std::min(16777216.0, std::floor(tc.keep_prob * 16777216.0)) : 0u;
     auto in_ptr = [&](const TLayer& L, float** g) -> const float* {
@@ -514,6 +524,7 @@ static int read_stats(dcscn_ctx* h, TrainState* t, double* stats, hipStream_t st
 // prepare_step, behind the validation: the device, the arena of the batch shape, the stream the step runs on (null: the handle's)
 static int prepare_step(dcscn_ctx* h, int n, int H, int W, void* stream, TrainState** t, hipStream_t* st) {
     *t = h->train;
+    (*t)->acts_valid = false;   // (whatever runs next overwrites the last log pass's activations)
     HIP_TRY(h, hipSetDevice(h->device));
     *st = stream ? (hipStream_t)stream : h->stream;
     return carve(h, *t, n, H, W);
@@ -569,6 +580,90 @@ static int write_record(dcscn_ctx* h, TrainState* t, int n, float* rec, hipStrea
     return join_stream(h, st);
 }
 
+// ---------------------------------------------------------------------------------------------
+// log pass (include/dcscn.h: dcscn_train_log_pass)
+// ---------------------------------------------------------------------------------------------
+// y_ = the last layer + x2 (DCSCN.py:325); a step never stores it (tloss forms it on the fly)
+__global__ void tadd_out(const float* z, const float* x2, int64_t count, float* y) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < count) y[e] = z[e] + x2[e];
+}
+
+// What the reference appends to self.H for the layer: the activator's output (with dropout off: exactly that) in the layer's slice of its
+// output buffer; Up-TCNN's output buffer; else the conv's output z -- for an Up-PS conv the tensor before depth_to_space.
+static SummaryView output_view(const TrainState* t, const TLayer& L) {
+    if (L.dropout || L.up > 0) {
+        const TBuf& ob = t->bufs[L.out_buf];
+        const int64_t px = L.up > 0 ? L.px * L.up * L.up : L.px;
+        return SummaryView{ob.h + L.out_off, px * L.cout, L.cout, ob.stride};
+    }
+    return flat_view(L.z, L.zcount);
+}
+
+// "x", "y_" and "<layer>/output" of the current carve; false: no such activation
+static bool activation_view(dcscn_ctx* h, const std::string& name, SummaryView* v) {
+    const TrainState* t = h->train;
+    if (!t) return false;
+    const int64_t P = (int64_t)t->n * t->H * t->W, hr = P * h->cfg.scale * h->cfg.scale;
+    if (name == "x") { *v = flat_view(t->io_x, P); return true; }
+    if (name == "y_") { *v = flat_view(t->at, hr); return true; }   // (tadd_out's destination: `at` is free behind the backward pass)
+    if (!ends_with(name, "/output")) return false;
+    const std::string layer = name.substr(0, name.size() - 7);
+    for (const TLayer& L : t->layers)
+        if (L.name == layer) { *v = output_view(t, L); return true; }
+    return false;
+}
+
+static int log_pass(dcscn_ctx* h, const float* x, const float* x2, const float* y, int n, int H, int W, double* stats) {
+    int rc = check_step(h, x, x2, y, n, H, W);
+    if (rc) return rc;
+    TrainState* t;
+    hipStream_t st;
+    if ((rc = prepare_step(h, n, H, W, nullptr, &t, &st))) return rc;
+    t->sum_valid = false;
+    const int s = h->cfg.scale;
+    const int64_t P = (int64_t)n * H * W, hr = P * s * s;
+    HIP_TRY(h, hipMemcpyAsync(t->io_x, x, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t->io_x2, x2, (size_t)hr * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(t->io_y, y, (size_t)hr * 4, hipMemcpyHostToDevice, st));
+    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, 0, st, 0, false))) return rc;
+    KTRY(h, hipLaunchKernelGGL(tadd_out, dim3(grid1(hr)), dim3(256), 0, st, (const float*)t->zlast, (const float*)t->io_x2, hr, t->at));
+    if (t->sum_names.empty()) {
+        for (const TensorSpec& ts : h->tensors) { t->sum_names.push_back(ts.name); t->sum_names.push_back(ts.name + "/grad"); }
+        for (const TLayer& L : t->layers) t->sum_names.push_back(L.name + "/output");
+        t->sum_names.push_back("x");
+        t->sum_names.push_back("y_");
+        for (size_t i = 0; i < t->sum_names.size(); ++i) t->sum_index[t->sum_names[i]] = (int)i;
+    }
+    const size_t names = t->sum_names.size(), head = names * (sizeof(dcscn_summary) + sizeof(int64_t) * kSummaryBuckets);
+    if ((rc = grow(h, &t->sum_dev, &t->sum_cap, head + summary_scratch_bytes(), st))) return rc;
+    HIP_TRY(h, summary_prepare_device(h->device));
+    dcscn_summary* recs = reinterpret_cast<dcscn_summary*>(t->sum_dev);
+    int64_t* counts = reinterpret_cast<int64_t*>(t->sum_dev + names * sizeof(dcscn_summary));
+    HIP_TRY(h, hipMemsetAsync(t->sum_dev, 0, head, st));
+    size_t r = 0;
+    auto reduce = [&](const SummaryView& v) {
+        const hipError_t e = launch_summary(v, t->sum_dev + head, recs + r, counts + r * kSummaryBuckets, st);
+        ++r;
+        return e;
+    };
+    for (size_t i = 0; i < h->tensors.size(); ++i) {   // (the order of sum_names)
+        const int64_t c = (int64_t)h->tensors[i].data.size();
+        HIP_TRY(h, reduce(flat_view(t->d_w + t->off[i], c)));
+        HIP_TRY(h, reduce(flat_view(t->d_g + t->off[i], c)));
+    }
+    for (const TLayer& L : t->layers) HIP_TRY(h, reduce(output_view(t, L)));
+    HIP_TRY(h, reduce(flat_view(t->io_x, P)));
+    HIP_TRY(h, reduce(flat_view(t->at, hr)));
+    t->sum_host.resize(head);
+    HIP_TRY(h, hipMemcpyAsync(t->sum_host.data(), t->sum_dev, head, hipMemcpyDeviceToHost, st));
+    if (stats) HIP_TRY(h, hipMemcpyAsync(stats, t->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));   // the pass's one synchronisation
+    t->sum_valid = true;
+    t->acts_valid = true;
+    return DCSCN_OK;
+}
+
 void train_free(dcscn_ctx* h) {
     TrainState* t = h->train;
     if (!t) return;
@@ -576,6 +671,7 @@ void train_free(dcscn_ctx* h) {
         if (p) (void)hipFree(p);
     if (t->d_red) (void)hipFree(t->d_red);
     if (t->join_ev) (void)hipEventDestroy(t->join_ev);
+    if (t->sum_dev) (void)hipFree(t->sum_dev);
     if (t->arena) (void)hipFree(t->arena);
     delete t;
     h->train = nullptr;
@@ -662,6 +758,27 @@ int dcscn_train_step(dcscn_handle h, const float* x, const float* x2, const floa
 int dcscn_train_gradients(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width,
                           uint64_t dropout_key, double* stats) {
     return host_step(h, x, x2, y_true, n, height, width, 0.0, dropout_key, stats, false);
+}
+
+int dcscn_train_log_pass(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width, double* stats) {
+    return log_pass(h, x, x2, y_true, n, height, width, stats);
+}
+
+int dcscn_summary_get(dcscn_handle h, const char* name, dcscn_summary* out, int64_t* buckets, int capacity) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    if (!name || !out) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_summary_get: null argument");
+    if (buckets && capacity < kSummaryBuckets)
+        return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_summary_get: room for %d bucket counts, %d needed", capacity, kSummaryBuckets);
+    const TrainState* t = h->train;
+    if (!t || !t->sum_valid) return fail(h, DCSCN_ERR_STATE, "dcscn_summary_get before dcscn_train_log_pass");
+    const auto it = t->sum_index.find(name);
+    if (it == t->sum_index.end()) return fail(h, DCSCN_ERR_SHAPE, "no summary '%s'", name);
+    const size_t names = t->sum_names.size();
+    memcpy(out, t->sum_host.data() + (size_t)it->second * sizeof(dcscn_summary), sizeof(dcscn_summary));
+    if (buckets)
+        memcpy(buckets, t->sum_host.data() + names * sizeof(dcscn_summary) + (size_t)it->second * kSummaryBuckets * sizeof(int64_t),
+               kSummaryBuckets * sizeof(int64_t));
+    return DCSCN_OK;
 }
 
 int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width, double lr,
@@ -798,6 +915,16 @@ int dcscn_get_tensor(dcscn_handle h, const char* name, float* out, int64_t count
     float* dev = nullptr;
     int64_t n = 0;
     bool is_var;
+    SummaryView av;
+    if (activation_view(h, name, &av)) {   // "x", "y_", "<layer>/output": what the last log pass left in the arena
+        if (!h->train->acts_valid) return fail(h, DCSCN_ERR_STATE, "'%s' is readable only between dcscn_train_log_pass and the next training call", name);
+        if (count != av.count) return fail(h, DCSCN_ERR_SHAPE, "tensor '%s' has %lld values, not %lld", name, (long long)av.count, (long long)count);
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (av.C == av.stride) HIP_TRY(h, hipMemcpy(out, av.p, (size_t)av.count * 4, hipMemcpyDeviceToHost));
+        else HIP_TRY(h, hipMemcpy2D(out, (size_t)av.C * 4, av.p, (size_t)av.stride * 4, (size_t)av.C * 4, (size_t)(av.count / av.C), hipMemcpyDeviceToHost));
+        return DCSCN_OK;
+    }
     int rc = train_tensor(h, name, &dev, &n, &is_var);
     if (rc) return rc;
     if (count != n) return fail(h, DCSCN_ERR_SHAPE, "tensor '%s' has %lld values, not %lld", name, (long long)n, (long long)count);

@@ -34,7 +34,10 @@ EXPORTED_SYMBOLS = (
     "dcscn_train_record_floats", "dcscn_train_local_gradients_device", "dcscn_train_local_gradients_patches",
     "dcscn_train_apply_records",
     "dcscn_resample_table_bytes", "dcscn_resize_bicubic_bytes", "dcscn_resize_bicubic_bytes_device", "dcscn_sr_rgb_bytes",
+    "dcscn_summary_bucket_limits", "dcscn_summarize_device", "dcscn_train_log_pass", "dcscn_summary_get",
 )
+
+SUMMARY_BUCKETS = 1551
 
 # dcscn_optimizer; the names of helper/args.py --optimizer
 OPTIMIZERS = {"adam": 0, "gd": 1, "momentum": 2, "adadelta": 3, "adagrad": 4, "rmsprop": 5}
@@ -131,6 +134,26 @@ class Metrics(ctypes.Structure):
     ]
 
 
+class Summary(ctypes.Structure):
+    """dcscn_summary: the record of one summarised tensor ("TensorBoard summaries" in include/dcscn.h)."""
+    _fields_ = [
+        ("num", ctypes.c_int64),
+        ("nonfinite", ctypes.c_int64),
+        ("min", ctypes.c_double),
+        ("max", ctypes.c_double),
+        ("sum", ctypes.c_double),
+        ("sum_squares", ctypes.c_double),
+        ("mean", ctypes.c_double),
+        ("stddev", ctypes.c_double),
+    ]
+
+    def as_dict(self, buckets=None):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        if buckets is not None:
+            d["buckets"] = buckets
+        return d
+
+
 _lib = None
 
 
@@ -210,6 +233,11 @@ def load_library():
     lib.dcscn_train_local_gradients_device.argtypes = [vp, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_uint64, c.c_int64, vp, vp]
     lib.dcscn_train_local_gradients_patches.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_uint64, c.c_int64, vp, vp]
     lib.dcscn_train_apply_records.argtypes = [vp, vp, c.c_int, c.c_double, dp, vp]
+    i64p = c.POINTER(c.c_int64)
+    lib.dcscn_summary_bucket_limits.argtypes = [dp, c.c_int]
+    lib.dcscn_summarize_device.argtypes = [vp, vp, c.c_int64, c.POINTER(Summary), i64p, c.c_int, vp]
+    lib.dcscn_train_log_pass.argtypes = [vp, fp, fp, fp, c.c_int, c.c_int, c.c_int, dp]
+    lib.dcscn_summary_get.argtypes = [vp, c.c_char_p, c.POINTER(Summary), i64p, c.c_int]
     if lib.dcscn_abi_version() != ABI_VERSION:
         raise EngineError(5, "ABI mismatch: library %d, binding %d" % (lib.dcscn_abi_version(), ABI_VERSION))
     _lib = lib
@@ -276,6 +304,17 @@ def make_train_config(flags):
     c.clipping_norm = float(get("clipping_norm", 5))
     c.keep_prob = float(get("dropout_rate", 0.8))
     return c
+
+
+def summary_bucket_limits():
+    """The SUMMARY_BUCKETS float64 limits of the summary histograms (dcscn_summary_bucket_limits: TensorFlow's default table, built
+    on the host by the library); needs no GPU."""
+    lib = load_library()
+    out = np.zeros(SUMMARY_BUCKETS, np.float64)
+    n = lib.dcscn_summary_bucket_limits(out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size)
+    if n != SUMMARY_BUCKETS:
+        raise EngineError(5, "the library has %d summary buckets, the binding %d" % (n, SUMMARY_BUCKETS))
+    return out
 
 
 def resample_table(in_size, out_size):
@@ -626,7 +665,68 @@ class Engine:
                                                         ctypes.c_void_p(stream) if stream else None))
         return tuple(stats) if want_stats else None
 
+    # ---- TensorBoard summaries ("TensorBoard summaries" in include/dcscn.h) ----
+    def summarize_device(self, data_ptr, count, stream=None, want_buckets=True):
+        """The summary record of ``count`` float32 values at the device pointer ``data_ptr`` (e.g. ``torch.Tensor.data_ptr()``), reduced
+        on the device: a dict of num, nonfinite, min, max, sum, sum_squares, mean, stddev and, with want_buckets, "buckets", the
+        SUMMARY_BUCKETS int64 counts over summary_bucket_limits().  Synchronises ``stream`` (None / 0 = the handle's own)."""
+        rec = Summary()
+        buckets = np.zeros(SUMMARY_BUCKETS, np.int64) if want_buckets else None
+        self._check(self._lib.dcscn_summarize_device(
+            self._h, ctypes.c_void_p(data_ptr), int(count), ctypes.byref(rec),
+            buckets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if want_buckets else None, SUMMARY_BUCKETS if want_buckets else 0,
+            ctypes.c_void_p(stream) if stream else None))
+        return rec.as_dict(buckets)
+
+    def train_log_pass(self, x, x2, y_true):
+        """What the reference's summary run computes: forward and backward of the host batch with dropout off, no update, then every
+        summarised tensor reduced on the device.  Returns the stats of train_step; afterwards summary(name) reads a record, and
+        until the next training call get_tensor reads "<var>/grad" of this pass, "<layer>/output", "x" and "y_"."""
+        x, x2, y_true, n, h, w = self._train_arrays(x, x2, y_true)
+        fp = ctypes.POINTER(ctypes.c_float)
+        stats = (ctypes.c_double * 4)()
+        self._check(self._lib.dcscn_train_log_pass(self._h, x.ctypes.data_as(fp), x2.ctypes.data_as(fp), y_true.ctypes.data_as(fp), n, h, w, stats))
+        self._log_shape = (n, h, w)
+        return tuple(stats)
+
+    def summary_names(self):
+        """The names summary() knows after a log pass: every variable, its "/grad", "<layer>/output" per layer, "x", "y_"."""
+        names = []
+        for n, _ in self.tensor_specs():
+            names += [n, n + "/grad"]
+        return names + [l["name"] + "/output" for l in self.layers()] + ["x", "y_"]
+
+    def summary(self, name, want_buckets=True):
+        """The record of ``name`` from the last train_log_pass, as summarize_device returns it."""
+        rec = Summary()
+        buckets = np.zeros(SUMMARY_BUCKETS, np.int64) if want_buckets else None
+        self._check(self._lib.dcscn_summary_get(self._h, name.encode(), ctypes.byref(rec),
+                                                buckets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if want_buckets else None,
+                                                SUMMARY_BUCKETS if want_buckets else 0))
+        return rec.as_dict(buckets)
+
+    def _activation_shape(self, name):
+        """Shape of "x", "y_" or "<layer>/output" for the batch of the last log pass; None: not such a name."""
+        shape = getattr(self, "_log_shape", None)
+        if shape is None:
+            return None
+        n, h, w = shape
+        s = self.scale
+        if name == "x":
+            return (n, h, w, 1)
+        if name == "y_":
+            return (n, h * s, w * s, 1)
+        if name.endswith("/output"):
+            for l in self.layers():
+                if l["name"] == name[:-len("/output")]:
+                    r = l["resolution"] * (s if l["name"] == "Up-TCNN" else 1)    # (the transposed conv's output is upscaled)
+                    return (n, h * r, w * r, l["out_channels"])
+        return None
+
     def _numel(self, name):
+        act = self._activation_shape(name)
+        if act is not None:
+            return act
         base = name
         for suffix in ("/grad", "/Adam_1", "/Adam", "/Momentum"):
             if name.endswith(suffix):
@@ -641,7 +741,8 @@ class Engine:
 
     def get_tensor(self, name):
         """A variable (the trained value while training), "<var>/grad", a slot ("<var>/Adam", "<var>/Adam_1",
-        "<var>/Momentum") or "beta1_power" / "beta2_power", shaped like the checkpoint variable."""
+        "<var>/Momentum") or "beta1_power" / "beta2_power", shaped like the checkpoint variable; between a train_log_pass and the
+        next training call also "<layer>/output" (NHWC), "x" and "y_" of that pass."""
         shape = self._numel(name)
         out = np.empty(shape, np.float32)
         self._check(self._lib.dcscn_get_tensor(self._h, name.encode(), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size))

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import ckpt, engine, frozen, imaging as util, shard
+from . import ckpt, engine, events, frozen, imaging as util, shard
 
 BICUBIC_METHOD_STRING = "bicubic"
 
@@ -138,6 +138,13 @@ class SuperResolution:
             self.total_epochs += self.lr_decay_epoch
             lr *= self.lr_decay
         self.log_filename = fget("log_filename", "log.txt")
+        # extension: write the reference's TensorBoard log (log_to_tensorboard); off = the no-op this model always had.  save_weights and
+        # initialize_tf_log are the reference's flags (tf_graph.py:44, DCSCN.py:98-100) and take effect only with it
+        self.tensorboard = bool(fget("tensorboard", False))
+        self.save_weights = bool(fget("save_weights", True)) and bool(self.enable_log)
+        self.initialize_tf_log = bool(fget("initialize_tf_log", True))
+        self._train_writer = None           # events.EventWriter on <tf_log_dir>/train, opened by the first log_to_tensorboard that writes
+        self._log_image_size = None         # the size of the logged image when it had to be cut to fit the training workspace
         self.train = None
         self.lr = self.initial_lr
         self.step = self.training_step = self.epochs_completed = self.epochs_completed_in_stage = 0
@@ -270,7 +277,8 @@ class SuperResolution:
                                  dropout_rate=self.dropout_rate, use_l1_loss=self.use_l1_loss)
 
     def build_summary_saver(self, with_saver=True):
-        """TensorBoard writers / Saver in the reference (tf_graph.py:298-305); nothing to create."""
+        """TensorBoard writers / Saver in the reference (tf_graph.py:298-305); nothing to create: the event writer of --tensorboard is opened
+        by the first log_to_tensorboard that writes."""
 
     def init_all_variables(self):
         """``tf.global_variables_initializer`` (tf_graph.py:73-75): He truncated-normal filters
@@ -390,6 +398,9 @@ class SuperResolution:
             self._engine.close()
             self._engine = None
         self._train_engine = None
+        if self._train_writer is not None:
+            self._train_writer.close()
+            self._train_writer = None
 
     # ---- training (DCSCN.py:146-190, 426-532, 727-769) ---------------------------------------------
     def load_dynamic_datasets(self, data_dir, batch_image_size):
@@ -527,7 +538,76 @@ class SuperResolution:
         self.step += 1
 
     def log_to_tensorboard(self, test_filename, psnr, save_meta_data=True):
-        """TensorBoard summaries (DCSCN.py:438-468): not written -- there is no TensorBoard here.  Deliberately a no-op."""
+        """TensorBoard summaries (DCSCN.py:427-479), written only with --tensorboard (and enable_log); otherwise a no-op.
+
+        One log pass of the engine on the test image (forward and backward with dropout off, every summary reduced on the device:
+        dcscn_train_log_pass), then one Event at step = epochs_completed with every summary of events.summary_plan, and the scalars
+        PSNR (the mean training PSNR; not with use_l1_loss or before any step) and LR, under <tf_log_dir>/train.  With save_weights
+        false only the scalars (Loss, L2WeightDecayLoss, PSNR, LR) are written.  In a data-parallel run rank 0 writes, from the first step on.
+        Departures: the reference's second writer (<tf_log_dir>/test: the graph and the test PSNR) is not written; an image that does
+        not fit the training workspace (training never tiles) is cut to half its longer side, from the top left, until it fits."""
+        if not (self.tensorboard and self.enable_log):
+            return
+        if self._data_parallel() and self.train_group.rank != 0:
+            return
+        if self._data_parallel() and not self._training_active():
+            # train.py's log before the first step: beginning the training here would be rank 0 alone in _ready_training's broadcast
+            logging.info("tensorboard: the log before the first step is not written in a data-parallel run")
+            return
+        eng = self._ready_training()
+        org_image = util.set_image_alignment(util.load_image(test_filename, print_console=False), self.scale)
+        if len(org_image.shape) >= 3 and org_image.shape[2] == 3 and self.channels == 1:
+            org_image = util.convert_rgb_to_y(org_image)
+        while True:
+            input_image = util.resize_image_by_pil(org_image, 1.0 / self.scale, resampling_method=self.resampling_method)
+            bicubic_image = util.resize_image_by_pil(input_image, self.scale, resampling_method=self.resampling_method)
+            batch = [input_image, bicubic_image, org_image]
+            if self.max_value != 255.0:
+                batch = [np.multiply(a, self.max_value / 255.0) for a in batch]
+            try:
+                stats = eng.train_log_pass(*[np.asarray(a, np.float32).reshape((1,) + a.shape[:2] + (1,)) for a in batch])
+                break
+            except engine.EngineError as exc:
+                if exc.status != 7:                                    # DCSCN_ERR_NOMEM
+                    raise
+                nomem = exc
+            h, w = org_image.shape[:2]
+            if h >= w:
+                h = h // 2 // self.scale * self.scale
+            else:
+                w = w // 2 // self.scale * self.scale
+            if h < self.scale or w < self.scale:
+                raise nomem
+            org_image = org_image[:h, :w]
+            if self._log_image_size is None or (h, w) < self._log_image_size:
+                self._log_image_size = (h, w)
+                logging.info("tensorboard: the logged image is cut to %d x %d to fit the training workspace" % (w, h))
+        values, records = [], {}
+        variables = [n for n, _ in eng.tensor_specs()]
+        for kind, tag, source, field in events.summary_plan(eng.layers(), variables, self.name, l2_decay=self.l2_decay, save_weights=self.save_weights):
+            if source == "loss":
+                values.append((tag, stats[3]))
+                continue
+            if source == "l2_loss":
+                values.append((tag, stats[3] - stats[0]))
+                continue
+            rec = records.get(source)
+            if rec is None:
+                rec = records[source] = eng.summary(source)
+            if rec["nonfinite"]:                                       # (TensorFlow's histogram op: "Nan in summary histogram for: ...")
+                raise ValueError("Nan in summary histogram for: %s (%d non-finite values)" % (tag, rec["nonfinite"]))
+            values.append((tag, rec[field] if kind == "scalar" else rec))
+        if self._train_writer is None:
+            util.make_dir(self.tf_log_dir)
+            if self.initialize_tf_log:
+                util.clean_dir(self.tf_log_dir)
+            self._train_writer = events.EventWriter(os.path.join(self.tf_log_dir, "train"), limits=engine.summary_bucket_limits())
+        writer = self._train_writer
+        writer.add_summary(values, self.epochs_completed)
+        if not self.use_l1_loss and self.training_step != 0:
+            writer.add_scalar("PSNR", self.training_psnr_sum / self.training_step, self.epochs_completed)
+        writer.add_scalar("LR", self.lr, self.epochs_completed)
+        writer.flush()
 
     def update_epoch_and_lr(self):
         self.epochs_completed_in_stage += 1

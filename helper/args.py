@@ -74,14 +74,14 @@ _TABLE = [
     (_S, "data_dir", "data", "directory of the image datasets"),
     (_S, "batch_dir", "batch_data", "directory of --build_batch patches (not supported)"),
     (_S, "output_dir", "output", "directory result images are written to"),
-    (_S, "tf_log_dir", "tf_log", "unused (no TensorBoard)"),
+    (_S, "tf_log_dir", "tf_log", "Directory for tensorboard log (written with --tensorboard)"),
     (_S, "log_filename", "log.txt", "log file"),
     (_S, "model_name", "", "explicit model name instead of the one derived from the flags"),
     (_S, "load_model_name", "", "checkpoint to load: a file stem or 'default'"),
     # ---- logging / device (args.py:88-94)
-    (_B, "initialize_tf_log", True, "unused"),
-    (_B, "enable_log", True, "unused"),
-    (_B, "save_weights", True, "unused"),
+    (_B, "initialize_tf_log", True, "Clear all tensorboard log before start (with --tensorboard)"),
+    (_B, "enable_log", True, "Enables tensorboard-log. Save loss. (with --tensorboard)"),
+    (_B, "save_weights", True, "Save weights and biases/gradients (with --tensorboard)"),
     (_B, "save_images", False, "unused"),
     (_I, "save_images_num", 20, "unused"),
     (_B, "save_meta_data", False, "unused"),
@@ -98,6 +98,8 @@ _TABLE = [
     (_B, "train_split16", False, "training at f32 accuracy with the forward and data-gradient convs of layers with min(cin, cout) >= 16 as three scaled f16 products"),
     # ---- extension (not a reference flag): the weight gradients of the same layers on the f16 matrix pipe (engine option "train_split16_wgrad", include/dcscn.h)
     (_B, "train_split16_wgrad", False, "training at f32 accuracy with the weight gradients of layers with min(cin, cout) >= 16 as three scaled f16 products"),
+    # ---- extension (not a reference flag): write the reference's TensorBoard log under <tf_log_dir>/train, summaries reduced on the device (dcscn_train_log_pass, include/dcscn.h)
+    (_B, "tensorboard", False, "write the TensorBoard event file of the reference's training log once per epoch (needs enable_log)"),
     # ---- frozen graphs (args.py:97-98): weights from the Const nodes of a frozen GraphDef (dcscn-super-resolution_amd/frozen.py)
     (_B, "frozenInference", False, "Flag for whether the model to evaluate is frozen."),
     (_S, "frozen_graph_path", "./model_to_freeze/frozen_model_optimized.pb", "the path to a frozen model if performing inference from it"),

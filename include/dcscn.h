@@ -595,6 +595,60 @@ int dcscn_get_tensor(dcscn_handle h, const char* name, float* out, int64_t count
 /* Write a variable or a slot of a training handle (resume from a checkpoint). */
 int dcscn_set_train_tensor(dcscn_handle h, const char* name, const float* data, int64_t count);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * TensorBoard summaries (util.add_summaries, helper/utilty.py:427-443; log_to_tensorboard, DCSCN.py:427-479), reduced on the device.
+ *
+ * A record summarises `count` float32 values:
+ *   num, nonfinite     the finite values, and the NaN / +Inf / -Inf ones: those are counted and left out of everything else
+ *                      (TensorFlow's histogram op refuses them; the caller decides what to do with a tensor that has some)
+ *   min, max           of the finite values
+ *   sum, sum_squares   double sums of (double)v and (double)v * (double)v
+ *   mean               sum / num                                    (tf.reduce_mean)
+ *   stddev             sqrt(mean((v - mean)^2)), a second pass over the data in double with the first pass's mean   (utilty.py:430-436)
+ *   buckets            DCSCN_SUMMARY_BUCKETS dense int64 counts: v is counted in bucket upper_bound(limits, (double)v), `limits` the
+ *                      table of dcscn_summary_bucket_limits
+ * num == 0 (no finite value, or count == 0 values in a view): min = max = sum = sum_squares = mean = stddev = 0.
+ * The limit table is TensorFlow's default histogram table as its histogram.cc builds it: for (v = 1e-12; v < 1e20; v *= 1.1) in double gives
+ * 774 positive limits p; limits = -DBL_MAX, -p reversed, 0.0, p, DBL_MAX.  It is built once on the host by exactly that loop and uploaded; the
+ * device searches the uploaded table (a binary search in LDS), it never recomputes a limit.  The table is written from memory of
+ * TensorFlow's source, not checked against it.
+ * Determinism: the values are cut into a fixed number of contiguous chunks, a function of `count` alone; every double sum runs over one chunk
+ * in a fixed order, and the chunks' sums are added in chunk order.  The counts use integer atomics, which commute exactly.  No floating-point
+ * atomic anywhere: two calls give the same bits.  The data pointer needs float alignment only; count may be 1.
+ * --------------------------------------------------------------------------------------------------------------------- */
+#define DCSCN_SUMMARY_BUCKETS 1551
+typedef struct dcscn_summary {
+    int64_t num, nonfinite;
+    double  min, max, sum, sum_squares, mean, stddev;
+} dcscn_summary;   /* 64 bytes */
+
+/* The bucket limits (host only, needs no device): writes min(capacity, DCSCN_SUMMARY_BUCKETS) doubles to `out` (may be NULL with
+ * capacity 0) and returns DCSCN_SUMMARY_BUCKETS. */
+int dcscn_summary_bucket_limits(double* out, int capacity);
+/* The record of `count` >= 1 float32 values at the DEVICE pointer `data`, reduced on `stream` (a hipStream_t, NULL = the handle's);
+ * `out` and `buckets` (optional; `capacity` >= DCSCN_SUMMARY_BUCKETS int64 values when given) are host memory, and the call returns
+ * after the stream has finished.  Needs neither dcscn_finalize nor dcscn_train_begin. */
+int dcscn_summarize_device(dcscn_handle h, const float* data, int64_t count, dcscn_summary* out, int64_t* buckets, int capacity,
+                           void* stream);
+/* What sess.run([summary_op, loss], {x, x2, y, dropout: 1.0, is_training: 0}) computes (DCSCN.py:446-471): forward and backward of the
+ * batch in host buffers as dcscn_train_gradients runs them -- the same launches, so whatever kernels the current "train_split16" options
+ * give a step -- but with dropout OFF whatever keep_prob the handle trains with; no update: variables, slots and beta powers are untouched.
+ * Then every summarised tensor is reduced on the handle's stream and the call synchronises once.  stats (optional): the 4 doubles of
+ * dcscn_train_step.  Afterwards, until the next gradient computation of any kind on the handle,
+ *   "<var>/grad"        reads THIS pass's gradients (dropout off), not the last step's;
+ *   dcscn_summary_get   returns the record of: every variable "<var>" and every "<var>/grad"; "<layer>/output" for each layer of
+ *                       dcscn_layer_info, the tensor the reference appends to self.H for it: the activator's output where the layer
+ *                       has one, else the conv's (for an Up-PS conv that is before depth_to_space), for Up-TCNN the transposed conv's;
+ *                       "x", the input; "y_", the last layer + x2;
+ *   dcscn_get_tensor    also reads "<layer>/output" (NHWC at the layer's resolution, n * H r * W r * out_channels values), "x" and "y_".
+ * The summaries stay readable after later steps; the three kinds of activations do not (DCSCN_ERR_STATE).
+ * The backward pass overwrites no activation (every layer keeps its own pre-activation and output in the training arena), so all
+ * records are taken behind it.  DCSCN_ERR_STATE before dcscn_train_begin; DCSCN_ERR_NOMEM as for a step (training never tiles). */
+int dcscn_train_log_pass(dcscn_handle h, const float* x, const float* x2, const float* y_true, int n, int height, int width, double* stats);
+/* The record `name` of the last dcscn_train_log_pass; buckets optional as above.  Before any log pass DCSCN_ERR_STATE; an unknown
+ * name DCSCN_ERR_SHAPE. */
+int dcscn_summary_get(dcscn_handle h, const char* name, dcscn_summary* out, int64_t* buckets, int capacity);
+
 const char* dcscn_last_error(dcscn_handle h);
 int dcscn_destroy(dcscn_handle h);
 
