@@ -207,9 +207,15 @@ def load_checkpoint(prefix, include_optimizer_slots=False):
     return tensors
 
 
+# TF's slot names behind a variable, per --optimizer (gd has none); adam adds the scalars beta1_power / beta2_power
+OPTIMIZER_SLOTS = {"adam": ("Adam", "Adam_1"), "momentum": ("Momentum",), "gd": (), "adagrad": ("Adagrad",),
+                   "adadelta": ("Adadelta", "Adadelta_1"), "rmsprop": ("RMSProp", "RMSProp_1")}
+
+
 def is_optimizer_slot(name):
     leaf = name.rsplit("/", 1)[-1]
-    return leaf in ("Adam", "Adam_1") or name in ("beta1_power", "beta2_power")
+    return (leaf in ("Adam", "Adam_1", "Adagrad", "Adadelta", "Adadelta_1", "RMSProp", "RMSProp_1")
+            or name in ("beta1_power", "beta2_power"))
 
 
 # ------------------------------------------------------------------------------------------------

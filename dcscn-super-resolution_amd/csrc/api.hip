@@ -380,7 +380,11 @@ int dcscn_set_option(dcscn_handle h, const char* key, int64_t value) {
         h->train_transposed = value != 0;
         return DCSCN_OK;
     }
-    if (!strcmp(key, "p16")) {                      // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
+    if (!strcmp(key, "train_optimizers")) {         // read by dcscn_train_begin alone: adadelta / adagrad / rmsprop are accepted; no effect on adam, momentum, gd
+        h->train_optimizers = value != 0;
+        return DCSCN_OK;
+    }
+    if (!strcmp(key, "p16")) {                     // any time: the next forward re-carves the workspace (1 = pre-split tensors between split16 launches)
         h->p16 = value != 0;
         return DCSCN_OK;
     }

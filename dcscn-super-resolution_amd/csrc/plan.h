@@ -268,7 +268,8 @@ struct dcscn_ctx {
     bool train_split16_wgrad = false;        // option "train_split16_wgrad": eligible weight gradients of the training plan on tconv_wgrad_h (train_wgrad_h.hpp)
     bool train_separable = false;            // option "train_separable": dcscn_train_begin builds the plan of a depthwise-separable net (train_dw.hpp) instead of refusing it
     bool train_transposed = false;           // option "train_transposed": dcscn_train_begin builds the plan of a transposed-conv net (train_tconv.hpp) instead of refusing it
-    dcscn_impl::TrainState* train = nullptr;      // train.hip: the training plan, variables and slots (dcscn_train_begin)
+    bool train_optimizers = false;           // option "train_optimizers": dcscn_train_begin accepts adadelta / adagrad / rmsprop (topt_more) instead of refusing them
+    dcscn_impl::TrainState* train = nullptr;     // train.hip: the training plan, variables and slots (dcscn_train_begin)
     dcscn_impl::TrainBatches* batches = nullptr;  // train_data.hip: device-resident training images and the batch planes
 };
 

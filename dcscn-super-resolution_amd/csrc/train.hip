@@ -491,9 +491,18 @@ static int run_gradients(dcscn_ctx* h, TrainState* t, const float* x, const floa
     return DCSCN_OK;
 }
 
-// the optimizer step on d_g scaled by clip[0]; ok: null, or a reduction's device flag that gates it (topt)
+// the three optimizers behind option "train_optimizers" (topt_more)
+static bool more_optimizer(int kind) { return kind == DCSCN_OPTIMIZER_ADADELTA || kind == DCSCN_OPTIMIZER_ADAGRAD || kind == DCSCN_OPTIMIZER_RMSPROP; }
+
+// the optimizer step on d_g scaled by clip[0]; ok: null, or a reduction's device flag that gates it (topt, topt_more)
 static int apply_update(dcscn_ctx* h, TrainState* t, double lr, const float* clip, const int* ok, hipStream_t st) {
     const dcscn_train_config& tc = t->tc;
+    if (more_optimizer(tc.optimizer)) {   // option "train_optimizers": adadelta, adagrad, rmsprop
+        KTRY(h, hipLaunchKernelGGL(topt_more, dim3(grid1(t->count)), dim3(256), 0, st, ok, tc.optimizer, t->d_w, (const float*)t->d_g, t->d_m, t->d_v, t->count,
+                                   clip, (float)lr, (float)tc.momentum));
+        t->stepped = true;
+        return DCSCN_OK;
+    }
     KTRY(h, hipLaunchKernelGGL(topt, dim3(grid1(t->count)), dim3(256), 0, st, ok, tc.optimizer, t->d_w, (const float*)t->d_g, t->d_m, t->d_v, t->count, clip,
                                (const float*)t->d_pw, (float)lr, (float)tc.beta1, (float)tc.beta2, (float)tc.epsilon, (float)tc.momentum));
     if (tc.optimizer == DCSCN_OPTIMIZER_ADAM) KTRY(h, hipLaunchKernelGGL(tpowers, dim3(1), dim3(1), 0, st, ok, t->d_pw, (float)tc.beta1, (float)tc.beta2));
@@ -710,7 +719,7 @@ int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc) {
     if (c.depthwise_separable && !h->train_separable) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of depthwise separable nets is not implemented");
     if (!c.pixel_shuffler && !h->train_transposed) return fail(h, DCSCN_ERR_UNSUPPORTED, "training of the transposed-conv upsampler (pixel_shuffler = false) is not implemented");
     if (c.batch_norm) return fail(h, DCSCN_ERR_UNSUPPORTED, "batch_norm is not implemented");
-    switch (tc->optimizer) {
+    if (!(h->train_optimizers && more_optimizer(tc->optimizer))) switch (tc->optimizer) {   // option "train_optimizers" lifts the three refusals
         case DCSCN_OPTIMIZER_ADAM: case DCSCN_OPTIMIZER_GD: case DCSCN_OPTIMIZER_MOMENTUM: break;
         case DCSCN_OPTIMIZER_ADADELTA: return fail(h, DCSCN_ERR_UNSUPPORTED, "optimizer adadelta is not implemented (supported: adam, gd, momentum)");
         case DCSCN_OPTIMIZER_ADAGRAD: return fail(h, DCSCN_ERR_UNSUPPORTED, "optimizer adagrad is not implemented (supported: adam, gd, momentum)");
@@ -741,6 +750,11 @@ int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc) {
     if (e == hipSuccess) e = hipMemset(t->d_g, 0, bytes);
     if (e == hipSuccess) e = hipMemset(t->d_m, 0, bytes);
     if (e == hipSuccess) e = hipMemset(t->d_v, 0, bytes);
+    // TF's non-zero initial slots: <var>/Adagrad = initial_accumulator_value, <var>/RMSProp = ones (the other three start at 0)
+    if (e == hipSuccess && (tc->optimizer == DCSCN_OPTIMIZER_ADAGRAD || tc->optimizer == DCSCN_OPTIMIZER_RMSPROP)) {
+        std::fill(flat.begin(), flat.end(), tc->optimizer == DCSCN_OPTIMIZER_ADAGRAD ? kAdagradInitialAccumulator : kRmsPropInitialMs);
+        e = hipMemcpy(t->d_m, flat.data(), bytes, hipMemcpyHostToDevice);
+    }
     t->h_pw[0] = (float)tc->beta1; t->h_pw[1] = (float)tc->beta2;      // TF: beta1_power / beta2_power start at beta1 / beta2
     if (e == hipSuccess) e = hipMemcpy(t->d_pw, t->h_pw, sizeof t->h_pw, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -873,7 +887,8 @@ int dcscn_train_apply_records(dcscn_handle h, const float* records, int world, d
     return DCSCN_OK;
 }
 
-// "<var>", "<var>/grad", "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power"
+// "<var>", "<var>/grad", "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "<var>/Adagrad", "<var>/Adadelta", "<var>/Adadelta_1", "<var>/RMSProp",
+// "<var>/RMSProp_1", "beta1_power", "beta2_power"
 static int train_tensor(dcscn_ctx* h, const char* name, float** dev, int64_t* count, bool* is_var) {
     TrainState* t = h->train;
     *is_var = false;
@@ -905,6 +920,11 @@ static int train_tensor(dcscn_ctx* h, const char* name, float** dev, int64_t* co
     else if (suffix == "Adam" && opt == DCSCN_OPTIMIZER_ADAM) *dev = t->d_m + t->off[i];
     else if (suffix == "Adam_1" && opt == DCSCN_OPTIMIZER_ADAM) *dev = t->d_v + t->off[i];
     else if (suffix == "Momentum" && opt == DCSCN_OPTIMIZER_MOMENTUM) *dev = t->d_m + t->off[i];
+    else if (suffix == "Adagrad" && opt == DCSCN_OPTIMIZER_ADAGRAD) *dev = t->d_m + t->off[i];
+    else if (suffix == "Adadelta" && opt == DCSCN_OPTIMIZER_ADADELTA) *dev = t->d_m + t->off[i];
+    else if (suffix == "Adadelta_1" && opt == DCSCN_OPTIMIZER_ADADELTA) *dev = t->d_v + t->off[i];
+    else if (suffix == "RMSProp" && opt == DCSCN_OPTIMIZER_RMSPROP) *dev = t->d_m + t->off[i];
+    else if (suffix == "RMSProp_1" && opt == DCSCN_OPTIMIZER_RMSPROP) *dev = t->d_v + t->off[i];
     else return fail(h, DCSCN_ERR_SHAPE, "unknown tensor '%s' for this optimizer", name);
     return DCSCN_OK;
 }

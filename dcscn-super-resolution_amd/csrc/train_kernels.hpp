@@ -357,6 +357,36 @@ __global__ void topt(const int* ok, int kind, float* w, const float* g, float* m
         w[e] = w[e] - lr * gg;
     }
 }
+// The three rules behind option "train_optimizers" (adagrad, adadelta, rmsprop), which topt does not know: same ok gate, clip scaling, flat
+// buffers and grid.  The reference constructs the optimizers with TF 1.x's defaults (DCSCN.py:383-392), so the constants are fixed here:
+// AdadeltaOptimizer rho 0.95, epsilon 1e-8; AdagradOptimizer initial_accumulator_value 0.1 (filled by dcscn_train_begin);
+// RMSPropOptimizer decay 0.9, epsilon 1e-10, not centred, momentum = --momentum (mu).  Each rule takes its operations in the order of TF's
+// ApplyAdagrad / ApplyAdadelta / ApplyRMSProp functors, one float32 rounding per operation (train.hip: fp contract(off)).
+static constexpr float kAdadeltaRho = 0.95f, kAdadeltaEps = 1e-8f, kAdagradInitialAccumulator = 0.1f;
+static constexpr float kRmsPropDecay = 0.9f, kRmsPropEps = 1e-10f, kRmsPropInitialMs = 1.0f;
+__global__ void topt_more(const int* ok, int kind, float* w, const float* g, float* m, float* v, int64_t count, const float* clip, float lr, float mu) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count || (ok && !ok[0])) return;
+    const float gg = g[e] * clip[0];
+    if (kind == DCSCN_OPTIMIZER_ADAGRAD) {            // m: <var>/Adagrad
+        const float a = m[e] + gg * gg;
+        m[e] = a;
+        w[e] = w[e] - lr * gg * (1.0f / sqrtf(a));
+    } else if (kind == DCSCN_OPTIMIZER_ADADELTA) {    // m: <var>/Adadelta (accum), v: <var>/Adadelta_1 (accum_update)
+        const float rho = kAdadeltaRho, eps = kAdadeltaEps;
+        const float a = m[e] * rho + gg * gg * (1.0f - rho);
+        const float u = sqrtf(v[e] + eps) * (1.0f / sqrtf(a + eps)) * gg;
+        w[e] = w[e] - u * lr;
+        v[e] = v[e] * rho + u * u * (1.0f - rho);
+        m[e] = a;
+    } else {                                          // DCSCN_OPTIMIZER_RMSPROP; m: <var>/RMSProp (ms), v: <var>/RMSProp_1 (mom)
+        const float s = m[e] + (gg * gg - m[e]) * (1.0f - kRmsPropDecay);
+        const float q = v[e] * mu + (gg * lr) / sqrtf(s + kRmsPropEps);
+        w[e] = w[e] - q;
+        m[e] = s;
+        v[e] = q;
+    }
+}
 // beta1_power / beta2_power behind an adam step; ok as topt's
 __global__ void tpowers(const int* ok, float* pw, float b1, float b2) {
     if (threadIdx.x == 0 && blockIdx.x == 0 && (!ok || ok[0])) { pw[0] = pw[0] * b1; pw[1] = pw[1] * b2; }

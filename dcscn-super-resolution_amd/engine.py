@@ -39,8 +39,9 @@ EXPORTED_SYMBOLS = (
 
 SUMMARY_BUCKETS = 1551
 
-# dcscn_optimizer; the names of helper/args.py --optimizer
+# dcscn_optimizer; the names of helper/args.py --optimizer (the last three train behind option "train_optimizers")
 OPTIMIZERS = {"adam": 0, "gd": 1, "momentum": 2, "adadelta": 3, "adagrad": 4, "rmsprop": 5}
+MORE_OPTIMIZERS = ("adadelta", "adagrad", "rmsprop")
 
 
 class EngineError(RuntimeError):
@@ -556,7 +557,8 @@ class Engine:
     # ---- training (DCSCN.py:334-425; "Training" in include/dcscn.h) ----
     def train_begin(self, flags):
         """build_optimizer: ``flags`` holds the training flags of helper/args.py (optimizer, beta1, beta2, epsilon, momentum,
-        l2_decay, clipping_norm, dropout_rate = keep probability, use_l1_loss)."""
+        l2_decay, clipping_norm, dropout_rate = keep probability, use_l1_loss).  adadelta, adagrad and rmsprop are accepted once
+        ``set_option("train_optimizers", 1)`` was called on this handle, and refused without it."""
         c = make_train_config(flags)
         self._check(self._lib.dcscn_train_begin(self._h, ctypes.byref(c)))
         self.training = True
@@ -728,7 +730,7 @@ class Engine:
         if act is not None:
             return act
         base = name
-        for suffix in ("/grad", "/Adam_1", "/Adam", "/Momentum"):
+        for suffix in ("/grad", "/Adam_1", "/Adam", "/Momentum", "/Adagrad", "/Adadelta_1", "/Adadelta", "/RMSProp_1", "/RMSProp"):
             if name.endswith(suffix):
                 base = name[: -len(suffix)]
                 break
@@ -741,7 +743,8 @@ class Engine:
 
     def get_tensor(self, name):
         """A variable (the trained value while training), "<var>/grad", a slot ("<var>/Adam", "<var>/Adam_1",
-        "<var>/Momentum") or "beta1_power" / "beta2_power", shaped like the checkpoint variable; between a train_log_pass and the
+        "<var>/Momentum"; behind option "train_optimizers" "<var>/Adagrad", "<var>/Adadelta", "<var>/Adadelta_1", "<var>/RMSProp",
+        "<var>/RMSProp_1") or "beta1_power" / "beta2_power", shaped like the checkpoint variable; between a train_log_pass and the
         next training call also "<layer>/output" (NHWC), "x" and "y_" of that pass."""
         shape = self._numel(name)
         out = np.empty(shape, np.float32)

@@ -42,6 +42,34 @@ def transposed_conv_initial(scale, channels):
     return w
 
 
+def _truncated_normal(shape, stddev, rng):
+    """Stands for ``tf.truncated_normal``: a standard normal draw clipped at 2 sigma, where TensorFlow redraws what falls outside
+    (the one departure of every truncated normal here: a little mass sits exactly on +-2 sigma)."""
+    return np.clip(rng.standard_normal(shape), -2.0, 2.0).astype(np.float32) * np.float32(stddev)
+
+
+def initial_filter(shape, initializer, weight_dev, rng):
+    """The initial value of a conv_W / depthwise_W / pointwise_W of HWIO ``shape`` under --initializer and --weight_dev (``utilty.weight``,
+    utilty.py:393-413, as tf_graph.py calls it: ``stddev=weight_dev`` and ``uniform`` left False), drawn from the numpy Generator ``rng``."""
+    shape = tuple(int(d) for d in shape)
+    fan_in = shape[0] * shape[1] * shape[2]
+    if initializer == "he":
+        return _truncated_normal(shape, math.sqrt(2.0 / fan_in), rng)
+    if initializer == "xavier":                                      # uniform=False: the truncated-normal branch (utilty.py:355-357)
+        return _truncated_normal(shape, math.sqrt(3.0 / (fan_in + shape[0] * shape[1] * shape[3])), rng)
+    if initializer == "uniform":
+        return rng.uniform(-2.0 * weight_dev, 2.0 * weight_dev, shape).astype(np.float32)
+    if initializer == "stddev":
+        return _truncated_normal(shape, weight_dev, rng)
+    if initializer == "identity":                                    # He, then 1 at the centre tap of the channel diagonal
+        initial = _truncated_normal(shape, math.sqrt(2.0 / fan_in), rng)
+        if len(shape) == 4:
+            for k in range(min(shape[2], shape[3])):
+                initial[shape[0] // 2, shape[1] // 2, k, k] = 1.0
+        return initial
+    return np.zeros(shape, np.float32)                               # the reference's else branch: any other name
+
+
 def build_input_image(image, width=0, height=0, channels=1, scale=1, alignment=0, convert_ycbcr=True):
     """Crop / align / convert / downscale a loaded image into the network input (loader.py:42-67)."""
     if width != 0 and height != 0:
@@ -271,7 +299,8 @@ class SuperResolution:
     def build_optimizer(self):
         """DCSCN.py:334-413: loss (mse or l1, + l2_decay * sum of l2_loss over the filters), clip_by_global_norm, and the
         optimizer of --optimizer.  The engine's training plan is started on the first train_batch, after the variables
-        are initialised or restored; adadelta / adagrad / rmsprop are refused there."""
+        are initialised or restored; adadelta / adagrad / rmsprop run with TF 1.x's default constants, as the reference
+        constructs them (DCSCN.py:383-392), behind the engine's option "train_optimizers", which the first train_batch sets."""
         self._train_flags = dict(optimizer=self.optimizer, beta1=self.beta1, beta2=self.beta2, epsilon=self.epsilon,
                                  momentum=self.momentum, l2_decay=self.l2_decay, clipping_norm=self.clipping_norm,
                                  dropout_rate=self.dropout_rate, use_l1_loss=self.use_l1_loss)
@@ -281,8 +310,9 @@ class SuperResolution:
         by the first log_to_tensorboard that writes."""
 
     def init_all_variables(self):
-        """``tf.global_variables_initializer`` (tf_graph.py:73-75): He truncated-normal filters
-        (utilty.py:360-363), zero bias, PReLU slope 0.1, the bilinear Tconv_W of a transposed-conv net -- replaced by ``load_model`` for real use."""
+        """``tf.global_variables_initializer`` (tf_graph.py:73-75): filters drawn by --initializer (``initial_filter``; He
+        truncated-normal by default, utilty.py:360-363), zero bias, PReLU slope 0.1, the bilinear Tconv_W of a transposed-conv net --
+        replaced by ``load_model`` for real use."""
         if self._engine is None:
             self.build_graph()
         rng = np.random.default_rng()
@@ -290,8 +320,7 @@ class SuperResolution:
         for name, shape in self._engine.tensor_specs():
             leaf = name.rsplit("/", 1)[-1]
             if leaf in ("conv_W", "depthwise_W", "pointwise_W"):
-                std = math.sqrt(2.0 / (shape[0] * shape[1] * shape[2]))
-                tensors[name] = np.clip(rng.standard_normal(shape), -2.0, 2.0).astype(np.float32) * np.float32(std)
+                tensors[name] = initial_filter(shape, self.initializer, self.weight_dev, rng)
             elif leaf == "conv_B":
                 tensors[name] = np.zeros(shape, np.float32)
             elif leaf == "Tconv_W":
@@ -432,6 +461,8 @@ class SuperResolution:
                 eng.set_option("train_separable", 1)             # read by train_begin: without it a separable net is refused
             if not self.pixel_shuffler:
                 eng.set_option("train_transposed", 1)            # likewise for the transposed-conv upsampler
+            if self.optimizer in engine.MORE_OPTIMIZERS:
+                eng.set_option("train_optimizers", 1)            # likewise for adadelta, adagrad and rmsprop
             eng.train_begin(self._train_flags)
             if self.train_split16:
                 eng.set_option("train_split16", 1)
@@ -449,15 +480,12 @@ class SuperResolution:
         eng = self._engine
         names = [n for n, _ in eng.tensor_specs()]
         tensors = {n: eng.get_tensor(n) for n in names}
+        for n in names:
+            for slot in ckpt.OPTIMIZER_SLOTS[self.optimizer]:       # TF's slot names of --optimizer
+                tensors[n + "/" + slot] = eng.get_tensor(n + "/" + slot)
         if self.optimizer == "adam":
-            for n in names:
-                tensors[n + "/Adam"] = eng.get_tensor(n + "/Adam")
-                tensors[n + "/Adam_1"] = eng.get_tensor(n + "/Adam_1")
             tensors["beta1_power"] = eng.get_tensor("beta1_power")
             tensors["beta2_power"] = eng.get_tensor("beta2_power")
-        elif self.optimizer == "momentum":
-            for n in names:
-                tensors[n + "/Momentum"] = eng.get_tensor(n + "/Momentum")
         return tensors
 
     def init_epoch_index(self):

@@ -41,14 +41,14 @@ _TABLE = [
     # ---- training (args.py:39-59)
     (_B, "bicubic_init", True, "unused (the reference defines it but never reads it)"),
     (_F, "clipping_norm", 5, "clip the gradients by their global norm to this value; 0 = no clipping"),
-    (_S, "initializer", "he", "weight initialiser used before a checkpoint is loaded"),
-    (_F, "weight_dev", 0.01, "stddev of the initialiser when --initializer is stddev"),
+    (_S, "initializer", "he", "weight initialiser used before a checkpoint is loaded: he, xavier, uniform, stddev, identity (any other name: zeros)"),
+    (_F, "weight_dev", 0.01, "stddev of the initialiser when --initializer is stddev; half the range when it is uniform"),
     (_F, "l2_decay", 0.0001, "weight of the l2 loss of the conv filters"),
-    (_S, "optimizer", "adam", "adam, momentum or gd (adadelta, adagrad and rmsprop are not supported)"),
+    (_S, "optimizer", "adam", "adam, momentum, gd, adadelta, adagrad or rmsprop (the last three with TF 1.x's default constants; rmsprop takes --momentum)"),
     (_F, "beta1", 0.9, "beta1 of adam"),
     (_F, "beta2", 0.999, "beta2 of adam"),
     (_F, "epsilon", 1e-8, "epsilon of adam (TF placement: added to sqrt(v))"),
-    (_F, "momentum", 0.9, "momentum of the momentum optimizer"),
+    (_F, "momentum", 0.9, "momentum of the momentum and rmsprop optimizers"),
     (_I, "batch_num", 20, "patches per training step"),
     (_I, "batch_image_size", 48, "LR size of a training patch"),
     (_I, "stride_size", 0, "patch stride of --build_batch (not supported)"),

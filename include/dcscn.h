@@ -283,6 +283,9 @@ int dcscn_op_info_get(dcscn_handle h, int index, dcscn_op_info* out);
  * transposed-conv upsampler (pixel_shuffler = 0, layer Up-TCNN) instead of refusing it ("Training" below); with 0 the refusal, its status
  * and its text are unchanged.  No effect on pixel-shuffler configs, and none after dcscn_train_begin.  A net that is both separable and
  * transposed needs this option and "train_separable"; with one of them set the refusal names the other.
+ * "train_optimizers" (default 0; read by dcscn_train_begin alone): with 1, dcscn_train_begin accepts DCSCN_OPTIMIZER_ADADELTA, _ADAGRAD and
+ * _RMSPROP ("Training" below: the rules, the fixed constants, the slots) instead of refusing them; with 0 the refusal, its status and its
+ * text are unchanged.  No effect on adam, gd or momentum, whose kernel is not the one these three run, and none after dcscn_train_begin.
  * "graph_replay" (default 0; any time): a dcscn_forward_device call whose arguments repeat (same x / x2 / y pointers, shape and
  * stream) is captured into a hipGraph the second time it is seen and replayed from then on: one graph launch instead of the
  * pass's ~30 kernel launches (the launch gaps are 0.4 % of a 1024-patch pass of the L12 model, 3 % for the narrow nets).  The
@@ -443,6 +446,15 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  *             w <- w - lr_t * m / (sqrt(v) + epsilon);  then beta1_power *= b1, beta2_power *= b2 (float32, start at b1, b2)
  *   gd:       w <- w - lr g
  *   momentum: a <- mu a + g; w <- w - lr a  (not Nesterov)
+ * and, behind option "train_optimizers" (default 0, read by dcscn_train_begin alone: with 0 the three are refused as ever; no effect on
+ * adam, gd or momentum), with the defaults TF 1.x gives the optimizers the reference constructs (DCSCN.py:383-392; the constants are
+ * fixed, the layout of dcscn_train_config is unchanged), each line one float32 operation per operator, in this order:
+ *   adagrad:  a = acc + g g; acc <- a; w <- w - lr g (1 / sqrt(a))                                    acc starts at 0.1
+ *   adadelta: a = acc rho + g g (1 - rho); u = sqrt(upd + eps) (1 / sqrt(a + eps)) g; w <- w - u lr;
+ *             upd <- upd rho + u u (1 - rho); acc <- a                        rho = 0.95, eps = 1e-8; acc, upd start at 0
+ *   rmsprop:  s = ms + (g g - ms) (1 - decay); q = mom mu + (g lr) / sqrt(s + eps); w <- w - q; ms <- s; mom <- q
+ *                                     decay = 0.9, eps = 1e-10, mu = the config's momentum, not centred; ms starts at 1, mom at 0
+ * These three are written from knowledge of TF 1.x's ApplyAdagrad / ApplyAdadelta / ApplyRMSProp; they have not been run against TensorFlow.
  * Everything is deterministic: two identical sequences of calls give bit-identical variables and slots.
  *
  * Separable nets (depthwise_separable; option "train_separable", default 0, read by dcscn_train_begin: with 0 such a net is refused, the
@@ -497,7 +509,9 @@ int dcscn_num_presplit_tensors(dcscn_handle h);
  *
  * Variables, their gradients and the slots live on the device in flat f32 buffers, checkpoint (HWIO) layout.  Tensor names
  * (TF's, so checkpoints interoperate): "<var>", "<var>/grad" (gradient of the total loss BEFORE clipping, of the last step
- * or dcscn_train_gradients call), "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power".
+ * or dcscn_train_gradients call), "<var>/Adam", "<var>/Adam_1", "<var>/Momentum", "beta1_power", "beta2_power"; with "train_optimizers"
+ * "<var>/Adagrad" (acc), "<var>/Adadelta" (acc), "<var>/Adadelta_1" (upd), "<var>/RMSProp" (ms), "<var>/RMSProp_1" (mom).  A slot of
+ * another optimizer than the running one is DCSCN_ERR_SHAPE; the beta powers exist under adam only.
  * The first forward (any dcscn_forward* / evaluate / sr call) after a step re-packs the inference plan from the device
  * variables (Training); forwards before any step are unchanged.
  * The training workspace is separate from the inference one, sized per batch shape and bounded by "workspace_budget_bytes":
@@ -507,9 +521,9 @@ typedef enum dcscn_optimizer {
     DCSCN_OPTIMIZER_ADAM = 0,
     DCSCN_OPTIMIZER_GD = 1,
     DCSCN_OPTIMIZER_MOMENTUM = 2,
-    DCSCN_OPTIMIZER_ADADELTA = 3,   /* refused: DCSCN_ERR_UNSUPPORTED */
-    DCSCN_OPTIMIZER_ADAGRAD = 4,    /* refused */
-    DCSCN_OPTIMIZER_RMSPROP = 5     /* refused */
+    DCSCN_OPTIMIZER_ADADELTA = 3,   /* these three: option "train_optimizers"; without it refused, DCSCN_ERR_UNSUPPORTED */
+    DCSCN_OPTIMIZER_ADAGRAD = 4,
+    DCSCN_OPTIMIZER_RMSPROP = 5
 } dcscn_optimizer;
 
 /* Training flags of helper/args.py (optimizer, beta1, beta2, epsilon, momentum, l2_decay, clipping_norm, dropout_rate,
@@ -524,9 +538,10 @@ typedef struct dcscn_train_config {
     int32_t reserved[8];
 } dcscn_train_config;
 
-/* build_optimizer: after dcscn_finalize; copies the variables to the device master copy and zeroes the slots.
+/* build_optimizer: after dcscn_finalize; copies the variables to the device master copy and fills the slots with TF's initial values
+ * (zeros, but 0.1 in "<var>/Adagrad" and 1 in "<var>/RMSProp").
  * Refused (DCSCN_ERR_UNSUPPORTED): depthwise_separable unless option "train_separable" was set to 1 before this call, pixel_shuffler = 0
- * unless option "train_transposed" was, batch_norm, adadelta / adagrad / rmsprop. */
+ * unless option "train_transposed" was, adadelta / adagrad / rmsprop unless option "train_optimizers" was, batch_norm. */
 int dcscn_train_begin(dcscn_handle h, const dcscn_train_config* tc);
 /* One training step on host buffers (x [n, h, w], x2 and y_true [n, s*h, s*w]); synchronous.  stats (optional, 4 doubles):
  * image_loss, mse, global gradient norm before clipping, total loss (image_loss + the l2 term). */

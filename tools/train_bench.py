@@ -38,6 +38,11 @@ defaults with pixel_shuffler = false (its README's training command line), L7_x2
 --config L7_x2_T --no-torch is the profiler run's command (its pixel-shuffler twin at the same shape: --config L7_x2_PS32; L12_x2_T's is L12_x2).
 
     python tools/train_bench.py --transposed
+
+--optimizer NAME sets --optimizer of the plain run's handle (adadelta, adagrad and rmsprop behind option "train_optimizers"); a comma-separated
+list times one handle per name, alternating step by step in ONE process, and prints one JSON line with every median.
+
+    python tools/train_bench.py --optimizer adam,adagrad,adadelta,rmsprop
 """
 import argparse
 import json
@@ -98,8 +103,8 @@ def step_flops(cfg, n, h, w):
     return total
 
 
-def flags():
-    return dict(optimizer="adam", beta1=0.9, beta2=0.999, epsilon=1e-8, l2_decay=1e-4, clipping_norm=5.0, dropout_rate=0.8)
+def flags(optimizer="adam"):
+    return dict(optimizer=optimizer, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8, l2_decay=1e-4, clipping_norm=5.0, dropout_rate=0.8)
 
 
 def batch(cfg, n, h, w):
@@ -182,9 +187,9 @@ def bench_split16_wgrad(name, n, size, steps, warmup):
                 ratio_11_over_10=round(med[2] / med[1], 4), ratio_11_over_00=round(med[2] / med[0], 4))
 
 
-def hip_engine(cfg):
-    """A training handle on synthetic weights; a separable net gets option "train_separable" and a transposed-conv net option
-    "train_transposed", which train_begin reads."""
+def hip_engine(cfg, optimizer="adam"):
+    """A training handle on synthetic weights; a separable net gets option "train_separable", a transposed-conv net option
+    "train_transposed" and adadelta / adagrad / rmsprop option "train_optimizers", which train_begin reads."""
     from dcscn_amd import engine
     eng = engine.Engine(cfg, device=0)
     eng.load_weights(O.synthetic_weights(cfg, seed=0))
@@ -192,12 +197,39 @@ def hip_engine(cfg):
         eng.set_option("train_separable", 1)
     if not cfg["pixel_shuffler"]:
         eng.set_option("train_transposed", 1)
-    eng.train_begin(flags())
+    if optimizer in engine.MORE_OPTIMIZERS:
+        eng.set_option("train_optimizers", 1)
+    eng.train_begin(flags(optimizer))
     return eng
 
 
-def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wgrad=False):
-    eng = hip_engine(cfg)
+def bench_optimizers(name, optimizers, n, size, steps, warmup):
+    """One handle per optimizer with the same weights and batch, alternating step by step on one stream."""
+    cfg = O.make_config(**CONFIGS[name])
+    engs = [hip_engine(cfg, opt) for opt in optimizers]
+    x, x2, y = (torch.from_numpy(a).cuda() for a in batch(cfg, n, size, size))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    times = [[] for _ in engs]
+    for i in range(warmup + steps):
+        for k, eng in enumerate(engs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            eng.train_step_device(x.data_ptr(), x2.data_ptr(), y.data_ptr(), n, size, size, 1e-4, i, stream=stream.cuda_stream, want_stats=False)
+            b.record(stream)
+            b.synchronize()
+            if i >= warmup:
+                times[k].append(a.elapsed_time(b))
+    for eng in engs:
+        eng.close()
+    med = [float(np.median(t)) for t in times]
+    return dict(optimizer_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, optimizers=list(optimizers),
+                ms=[round(m, 4) for m in med], min_ms=[round(float(np.min(t)), 4) for t in times],
+                ratio_to_first=[round(m / med[0], 4) for m in med])
+
+
+def bench_hip(cfg, n, h, w, steps, warmup, train_split16=False, train_split16_wgrad=False, optimizer="adam"):
+    eng = hip_engine(cfg, optimizer)
     if train_split16:
         eng.set_option("train_split16", 1)
     if train_split16_wgrad:
@@ -382,11 +414,16 @@ def main():
     ap.add_argument("--train-split16-wgrad", action="store_true", help="set option train_split16_wgrad on the timed handle")
     ap.add_argument("--separable", action="store_true", help="time the separable nets' HIP step and torch step alternating in one process")
     ap.add_argument("--transposed", action="store_true", help="time the transposed-conv nets' HIP step and torch step alternating in one process")
+    ap.add_argument("--optimizer", default="adam",
+                    help="--optimizer of the timed handle; a comma-separated list times one handle each, alternating in one process")
     ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
     if a.library:
         from dcscn_amd import build
         build.LIB_PATH = os.path.abspath(a.library)
+    if "," in a.optimizer:
+        print(json.dumps(bench_optimizers(a.config, a.optimizer.split(","), a.batch, a.size, a.steps, a.warmup)), flush=True)
+        return
     if a.split16:
         for name in ("L12_x2", "L7_x2"):
             print(json.dumps(bench_split16(name, a.batch, a.size, a.steps, a.warmup)), flush=True)
@@ -407,9 +444,9 @@ def main():
     if a.torch_only:
         print(json.dumps({"torch_ms_per_step": bench_torch(cfg, a.batch, a.size, a.size, a.steps, a.warmup)}))
         return
-    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup, a.train_split16, a.train_split16_wgrad)
+    med, best = bench_hip(cfg, a.batch, a.size, a.size, a.steps, a.warmup, a.train_split16, a.train_split16_wgrad, a.optimizer)
     flops = step_flops(cfg, a.batch, a.size, a.size)
-    out = dict(config=a.config, batch=a.batch, lr_size=a.size, steps=a.steps, warmup=a.warmup, ms_per_step=round(med, 4),
+    out = dict(config=a.config, optimizer=a.optimizer, batch=a.batch, lr_size=a.size, steps=a.steps, warmup=a.warmup, ms_per_step=round(med, 4),
                ms_per_step_min=round(best, 4), conv_gflop_per_step=round(flops / 1e9, 3),
                conv_tflops=round(flops / (med * 1e-3) / 1e12, 3), fraction_of_f32_matrix_peak=round(flops / (med * 1e-3) / PEAK_F32_MATRIX, 4))
     if not a.no_torch:
