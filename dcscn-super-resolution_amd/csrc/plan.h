@@ -320,8 +320,21 @@ int repack_weights(dcscn_ctx* h);
 void train_free(dcscn_ctx* h);
 int train_sync_inference(dcscn_ctx* h);
 // train_data.hip: validate n patches; build them into device buffers x [n, L, L], x2 and y_true [n, L s, L s] on `stream`
-int check_patches(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value);
-int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value, float* x, float* x2, float* y_true,
+// The patches of a call: rows of dcscn_patch (4 fields, transform DCSCN_AUG_NONE) or of dcscn_patch_aug (5 fields)
+struct PatchList {
+    const int32_t* rows;
+    int fields;
+    PatchList(const dcscn_patch* p) : rows(reinterpret_cast<const int32_t*>(p)), fields(4) {}
+    PatchList(const dcscn_patch_aug* p) : rows(reinterpret_cast<const int32_t*>(p)), fields(5) {}
+    explicit operator bool() const { return rows != nullptr; }
+    dcscn_patch_aug operator[](int i) const {
+        const int32_t* r = rows + (size_t)i * fields;
+        return dcscn_patch_aug{r[0], r[1], r[2], r[3], fields == 5 ? r[4] : (int32_t)DCSCN_AUG_NONE};
+    }
+};
+static_assert(sizeof(dcscn_patch) == 4 * sizeof(int32_t) && sizeof(dcscn_patch_aug) == 5 * sizeof(int32_t), "patch descriptors are packed int32 rows");
+int check_patches(dcscn_ctx* h, PatchList p, int n, int lr_size, double max_value);
+int build_batch_device(dcscn_ctx* h, PatchList p, int n, int lr_size, double max_value, float* x, float* x2, float* y_true,
                        hipStream_t stream);
 void train_batches_free(dcscn_ctx* h);
 // exec.hip

@@ -589,6 +589,34 @@ static int write_record(dcscn_ctx* h, TrainState* t, int n, float* rec, hipStrea
     return join_stream(h, st);
 }
 
+// dcscn_train_step_patches and dcscn_train_step_patches_aug: the batch built on the device (train_data.hip), then the step
+static int step_patches(dcscn_ctx* h, PatchList patches, int n, int lr_size, double max_value, double lr, uint64_t dropout_key, double* stats) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    TrainState* t;
+    hipStream_t st;
+    if ((rc = prepare_step(h, n, lr_size, lr_size, nullptr, &t, &st))) return rc;   // the handle's stream only: nothing to join
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;
+    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st))) return rc;
+    return finish_update(h, t, true, lr, stats, st);
+}
+
+// dcscn_train_local_gradients_patches and dcscn_train_local_gradients_patches_aug
+static int local_gradients_patches(dcscn_ctx* h, PatchList patches, int n, int lr_size, double max_value, uint64_t dropout_key,
+                                   int64_t first_index, float* record_out, void* stream, const char* who) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    if ((rc = check_record(h, record_out, first_index, who))) return rc;
+    TrainState* t;
+    hipStream_t st;
+    if ((rc = prepare_step(h, n, lr_size, lr_size, stream, &t, &st))) return rc;
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;
+    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st, first_index))) return rc;
+    return write_record(h, t, n, record_out, st);
+}
+
 // ---------------------------------------------------------------------------------------------
 // log pass (include/dcscn.h: dcscn_train_log_pass)
 // ---------------------------------------------------------------------------------------------
@@ -809,15 +837,12 @@ int dcscn_train_step_device(dcscn_handle h, const float* x, const float* x2, con
 
 int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr, uint64_t dropout_key,
                              double* stats) {
-    if (!h) return DCSCN_ERR_INVALID_ARG;
-    int rc = check_patches(h, patches, n, lr_size, max_value);
-    if (rc) return rc;
-    TrainState* t;
-    hipStream_t st;
-    if ((rc = prepare_step(h, n, lr_size, lr_size, nullptr, &t, &st))) return rc;   // the handle's stream only: nothing to join
-    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;   // train_data.hip
-    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st))) return rc;
-    return finish_update(h, t, true, lr, stats, st);
+    return step_patches(h, patches, n, lr_size, max_value, lr, dropout_key, stats);
+}
+
+int dcscn_train_step_patches_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value, double lr,
+                                 uint64_t dropout_key, double* stats) {
+    return step_patches(h, patches, n, lr_size, max_value, lr, dropout_key, stats);
 }
 
 int64_t dcscn_train_record_floats(dcscn_handle h) {
@@ -841,16 +866,14 @@ int dcscn_train_local_gradients_device(dcscn_handle h, const float* x, const flo
 
 int dcscn_train_local_gradients_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, uint64_t dropout_key,
                                         int64_t first_index, float* record_out, void* stream) {
-    if (!h) return DCSCN_ERR_INVALID_ARG;
-    int rc = check_patches(h, patches, n, lr_size, max_value);
-    if (rc) return rc;
-    if ((rc = check_record(h, record_out, first_index, "dcscn_train_local_gradients_patches"))) return rc;
-    TrainState* t;
-    hipStream_t st;
-    if ((rc = prepare_step(h, n, lr_size, lr_size, stream, &t, &st))) return rc;
-    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, t->io_x, t->io_x2, t->io_y, st))) return rc;   // train_data.hip
-    if ((rc = run_gradients(h, t, t->io_x, t->io_x2, t->io_y, dropout_key, st, first_index))) return rc;
-    return write_record(h, t, n, record_out, st);
+    return local_gradients_patches(h, patches, n, lr_size, max_value, dropout_key, first_index, record_out, stream,
+                                   "dcscn_train_local_gradients_patches");
+}
+
+int dcscn_train_local_gradients_patches_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value,
+                                            uint64_t dropout_key, int64_t first_index, float* record_out, void* stream) {
+    return local_gradients_patches(h, patches, n, lr_size, max_value, dropout_key, first_index, record_out, stream,
+                                   "dcscn_train_local_gradients_patches_aug");
 }
 
 int dcscn_train_apply_records(dcscn_handle h, const float* records, int world, double lr, double* stats, void* stream) {

@@ -1,10 +1,12 @@
 // Training batches on the device (helper/loader.py DynamicDataSets.load_batch_image, loader.py:278-355 of the reference):
-// per patch a crop of HR = L s pixels of an image kept on the device, its Y (RGB) or its pixels (grey), fliplr, then
+// per patch a crop of HR = L s pixels of an image kept on the device -- or of one of its eight flipped / rotated variants
+// (the files augmentation.py writes, DCSCN_AUG_*: an index map over the same pixels, so one upload serves all eight) --
+// its Y (RGB) or its pixels (grey), fliplr, then
 // LR = bicubic 1/s and x2 = bicubic s of LR as Pillow computes them -- mode "F" for the float Y of RGB images, mode "L" (8-bit
 // fixed point) for grey images -- and the max_value / float32 cast rules of load_batch_image + train_batch (include/dcscn.h).
 //
 // A batch is, on one stream and without a host synchronisation:
-//   batch_gather  (1 launch per 32 patches)  crop + Y / grey + fliplr into compact HR planes (float32 for RGB patches, uint8
+//   batch_gather  (1 launch per 32 patches)  variant + crop + Y / grey + fliplr into compact HR planes (float32 for RGB patches, uint8
 //                                            for grey ones, numbered in batch order per kind); writes y_true
 //   resize_device (4 launches, RGB patches)  resample.hip's mode-"F" kernels: HR -> LR -> x2
 //   resize_device_bytes (4 launches, grey patches) resample.hip's 8-bpc kernels: HR -> LR -> x2 through uint8 intermediates
@@ -32,8 +34,9 @@ namespace {
 constexpr int kChunk = 32;          // patches per gather / finish launch (their descriptors travel as kernel arguments)
 
 struct PatchDesc {
-    const uint8_t* px;              // the image, [H, W, c] uint8
-    int32_t w, c, top, left, flip;
+    const uint8_t* px;              // the image, [h, w, c] uint8
+    int32_t h, w, c, top, left, flip;   // top, left: in the image as `code` transforms it ([w, h] for codes 4 .. 7)
+    int32_t code;                   // DCSCN_AUG_*
     int32_t slot;                   // index among the batch's patches of the same kind (c == 3: float planes, c == 1: uint8 planes)
 };
 struct PatchChunk {
@@ -45,6 +48,23 @@ __device__ __forceinline__ double luma(double r, double g, double b) {
     return __fma_rn(b, 25.064 / 256.0, __fma_rn(g, 129.057 / 256.0, r * (65.738 / 256.0))) + 16.0;
 }
 
+// Pixel (r, c) of the image as `code` transforms it -> its offset in the stored image [h, w]: the index maps of numpy's flipud,
+// fliplr and rot90 in augmentation.py's order (include/dcscn.h, DCSCN_AUG_*).  `code` is uniform over a workgroup.
+__device__ __forceinline__ size_t source_pixel(int code, int h, int w, int r, int c) {
+    int sr, sc;
+    switch (code) {
+        case DCSCN_AUG_V: sr = h - 1 - r; sc = c; break;
+        case DCSCN_AUG_H: sr = r; sc = w - 1 - c; break;
+        case DCSCN_AUG_HV: sr = h - 1 - r; sc = w - 1 - c; break;
+        case DCSCN_AUG_R1: sr = c; sc = w - 1 - r; break;
+        case DCSCN_AUG_R2: sr = h - 1 - c; sc = r; break;
+        case DCSCN_AUG_R1_V: sr = c; sc = r; break;
+        case DCSCN_AUG_R2_V: sr = h - 1 - c; sc = w - 1 - r; break;
+        default: sr = r; sc = c; break;
+    }
+    return (size_t)sr * w + sc;
+}
+
 // grid (ceil(HR^2 / 256), patches of the chunk); y_true is offset to the chunk's first patch
 __global__ __launch_bounds__(256) void batch_gather_kernel(PatchChunk pc, int hr, int mul, double scale, float* __restrict__ yf,
                                                            uint8_t* __restrict__ y8, float* __restrict__ y_true) {
@@ -53,7 +73,7 @@ __global__ __launch_bounds__(256) void batch_gather_kernel(PatchChunk pc, int hr
     if (idx >= hr2) return;
     const PatchDesc& d = pc.p[blockIdx.y];
     const int i = (int)(idx / hr), j = (int)(idx % hr);
-    const size_t src = (size_t)(d.top + i) * d.w + d.left + (d.flip ? hr - 1 - j : j);
+    const size_t src = source_pixel(d.code, d.h, d.w, d.top + i, d.left + (d.flip ? hr - 1 - j : j));
     double v;
     if (d.c == 1) {
         const uint8_t u = d.px[src];
@@ -91,7 +111,7 @@ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace
 
-int check_patches(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double max_value) {
+int check_patches(dcscn_ctx* h, PatchList p, int n, int lr_size, double max_value) {
     if (!h->train) return fail(h, DCSCN_ERR_STATE, "training batch before dcscn_train_begin");
     if (!p || n < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "training batch: %d patches (need >= 1 and a patch array)", n);
     if (lr_size < 1) return fail(h, DCSCN_ERR_INVALID_ARG, "training batch: lr_size %d < 1", lr_size);
@@ -99,19 +119,28 @@ int check_patches(dcscn_ctx* h, const dcscn_patch* p, int n, int lr_size, double
     const int64_t hr = (int64_t)lr_size * h->cfg.scale;
     const int count = h->batches ? (int)h->batches->images.size() : 0;
     for (int i = 0; i < n; ++i) {
-        const dcscn_patch& q = p[i];
+        const dcscn_patch_aug q = p[i];
         if (q.image < 0 || q.image >= count) return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: unknown image %d (%d added)", i, q.image, count);
         if (q.fliplr != 0 && q.fliplr != 1) return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: fliplr %d is not 0 or 1", i, q.fliplr);
+        if (q.transform < 0 || q.transform >= DCSCN_AUG_COUNT)
+            return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: transform %d is not one of 0 .. %d", i, q.transform, DCSCN_AUG_COUNT - 1);
         const TrainImage& im = h->batches->images[q.image];
-        if (q.top < 0 || q.left < 0 || q.top + hr > im.H || q.left + hr > im.W)
-            return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: the %lld x %lld crop at (top %d, left %d) is outside image %d (%d x %d)", i,
-                        (long long)hr, (long long)hr, q.top, q.left, q.image, im.H, im.W);
+        const bool turned = q.transform >= DCSCN_AUG_R1;      // the rotated variants are [W, H]
+        const int th = turned ? im.W : im.H, tw = turned ? im.H : im.W;
+        if (q.top < 0 || q.left < 0 || q.top + hr > th || q.left + hr > tw) {
+            if (q.transform == DCSCN_AUG_NONE)
+                return fail(h, DCSCN_ERR_INVALID_ARG, "patch %d: the %lld x %lld crop at (top %d, left %d) is outside image %d (%d x %d)", i,
+                            (long long)hr, (long long)hr, q.top, q.left, q.image, im.H, im.W);
+            return fail(h, DCSCN_ERR_INVALID_ARG,
+                        "patch %d: the %lld x %lld crop at (top %d, left %d) is outside image %d under transform %d (%d x %d)", i, (long long)hr,
+                        (long long)hr, q.top, q.left, q.image, q.transform, th, tw);
+        }
     }
     return DCSCN_OK;
 }
 
 // after check_patches; x [n, L, L], x2 and y_true [n, HR, HR] device buffers
-int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int L, double max_value, float* x, float* x2, float* y_true, hipStream_t st) {
+int build_batch_device(dcscn_ctx* h, PatchList p, int n, int L, double max_value, float* x, float* x2, float* y_true, hipStream_t st) {
     TrainBatches* b = h->batches;
     const int s = h->cfg.scale, HR = L * s;
     const size_t hr2 = (size_t)HR * HR, lr2 = (size_t)L * L;
@@ -134,8 +163,9 @@ int build_batch_device(dcscn_ctx* h, const dcscn_patch* p, int n, int L, double 
     const double scale = max_value / 255.0;
     std::vector<PatchChunk> chunks((n + kChunk - 1) / kChunk);
     for (int i = 0, nf = 0, ng = 0; i < n; ++i) {
-        const TrainImage& im = b->images[p[i].image];
-        chunks[i / kChunk].p[i % kChunk] = PatchDesc{im.px, im.W, im.C, p[i].top, p[i].left, p[i].fliplr, im.C == 1 ? ng++ : nf++};
+        const dcscn_patch_aug q = p[i];
+        const TrainImage& im = b->images[q.image];
+        chunks[i / kChunk].p[i % kChunk] = PatchDesc{im.px, im.H, im.W, im.C, q.top, q.left, q.fliplr, q.transform, im.C == 1 ? ng++ : nf++};
     }
     for (size_t c = 0; c < chunks.size(); ++c) {
         const int cnt = std::min(kChunk, n - (int)c * kChunk);
@@ -167,6 +197,28 @@ void train_batches_free(dcscn_ctx* h) {
     if (b->out) (void)hipFree(b->out);
     delete b;
     h->batches = nullptr;
+}
+
+// dcscn_train_build_batch and dcscn_train_build_batch_aug
+static int build_batch_host(dcscn_ctx* h, PatchList patches, int n, int lr_size, double max_value, float* x, float* x2, float* y_true,
+                            const char* who) {
+    if (!h) return DCSCN_ERR_INVALID_ARG;
+    int rc = check_patches(h, patches, n, lr_size, max_value);
+    if (rc) return rc;
+    if (!x || !x2 || !y_true) return fail(h, DCSCN_ERR_INVALID_ARG, "%s: null output buffer", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    TrainBatches* b = h->batches;
+    const int s = h->cfg.scale;
+    const size_t lr_n = (size_t)n * lr_size * lr_size, hr_n = lr_n * s * s;
+    hipStream_t st = h->stream;
+    if ((rc = grow(h, &b->out, &b->out_cap, lr_n + 2 * hr_n, st))) return rc;
+    float *dx = b->out, *dx2 = dx + lr_n, *dy = dx2 + hr_n;
+    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, dx, dx2, dy, st))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(x, dx, lr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(x2, dx2, hr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(y_true, dy, hr_n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return DCSCN_OK;
 }
 
 }  // namespace dcscn_impl
@@ -201,23 +253,12 @@ int dcscn_train_add_image(dcscn_handle h, const uint8_t* pixels, int height, int
 }
 
 int dcscn_train_build_batch(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, float* x, float* x2, float* y_true) {
-    if (!h) return DCSCN_ERR_INVALID_ARG;
-    int rc = check_patches(h, patches, n, lr_size, max_value);
-    if (rc) return rc;
-    if (!x || !x2 || !y_true) return fail(h, DCSCN_ERR_INVALID_ARG, "dcscn_train_build_batch: null output buffer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    TrainBatches* b = h->batches;
-    const int s = h->cfg.scale;
-    const size_t lr_n = (size_t)n * lr_size * lr_size, hr_n = lr_n * s * s;
-    hipStream_t st = h->stream;
-    if ((rc = grow(h, &b->out, &b->out_cap, lr_n + 2 * hr_n, st))) return rc;
-    float *dx = b->out, *dx2 = dx + lr_n, *dy = dx2 + hr_n;
-    if ((rc = build_batch_device(h, patches, n, lr_size, max_value, dx, dx2, dy, st))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x, dx, lr_n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(x2, dx2, hr_n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(y_true, dy, hr_n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return DCSCN_OK;
+    return build_batch_host(h, patches, n, lr_size, max_value, x, x2, y_true, "dcscn_train_build_batch");
+}
+
+int dcscn_train_build_batch_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value, float* x, float* x2,
+                                float* y_true) {
+    return build_batch_host(h, patches, n, lr_size, max_value, x, x2, y_true, "dcscn_train_build_batch_aug");
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "dcscn_psnr_ssim", "dcscn_evaluate_rgb_metrics",
     "dcscn_train_record_floats", "dcscn_train_local_gradients_device", "dcscn_train_local_gradients_patches",
     "dcscn_train_apply_records",
+    "dcscn_train_build_batch_aug", "dcscn_train_step_patches_aug", "dcscn_train_local_gradients_patches_aug",
     "dcscn_resample_table_bytes", "dcscn_resize_bicubic_bytes", "dcscn_resize_bicubic_bytes_device", "dcscn_sr_rgb_bytes",
     "dcscn_summary_bucket_limits", "dcscn_summarize_device", "dcscn_train_log_pass", "dcscn_summary_get",
 )
@@ -234,6 +235,11 @@ def load_library():
     lib.dcscn_train_local_gradients_device.argtypes = [vp, vp, vp, vp, c.c_int, c.c_int, c.c_int, c.c_uint64, c.c_int64, vp, vp]
     lib.dcscn_train_local_gradients_patches.argtypes = [vp, vp, c.c_int, c.c_int, c.c_double, c.c_uint64, c.c_int64, vp, vp]
     lib.dcscn_train_apply_records.argtypes = [vp, vp, c.c_int, c.c_double, dp, vp]
+    # the dcscn_patch_aug twins take their namesakes' arguments (an older build of the library, timed through
+    # tools/train_bench.py --library, has none of them: calling one there raises AttributeError)
+    for name in ("dcscn_train_build_batch", "dcscn_train_step_patches", "dcscn_train_local_gradients_patches"):
+        if hasattr(lib, name + "_aug"):
+            getattr(lib, name + "_aug").argtypes = getattr(lib, name).argtypes
     i64p = c.POINTER(c.c_int64)
     lib.dcscn_summary_bucket_limits.argtypes = [dp, c.c_int]
     lib.dcscn_summarize_device.argtypes = [vp, vp, c.c_int64, c.POINTER(Summary), i64p, c.c_int, vp]
@@ -615,28 +621,35 @@ class Engine:
 
     @staticmethod
     def _patches(patches):
-        """dcscn_patch array from (image id, top, left, fliplr) rows."""
-        p = np.ascontiguousarray(np.asarray(patches, dtype=np.int32).reshape(-1, 4))
-        return p, ctypes.c_void_p(p.ctypes.data)
+        """(rows, pointer, suffix of the entry point): a dcscn_patch array from (image id, top, left, fliplr) rows and "", or -- when
+        any row has a fifth field, the transform (imaging.AUGMENT_SUFFIXES) -- a dcscn_patch_aug array (transform 0 where a row has
+        none) and "_aug"."""
+        rows = [tuple(r) for r in patches]
+        fields = 5 if any(len(r) == 5 for r in rows) else 4
+        if fields == 5:
+            rows = [r + (0,) if len(r) == 4 else r for r in rows]
+        p = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1, fields))
+        return p, ctypes.c_void_p(p.ctypes.data), "_aug" if fields == 5 else ""
 
     def train_build_batch(self, patches, lr_size, max_value=255.0):
-        """The batch of (image id, top, left, fliplr) patches as helper/loader.py's load_batch_image builds it, on the device:
-        float32 (x [n, lr_size, lr_size, 1], x2 [n, hr, hr, 1], y_true [n, hr, hr, 1]) with hr = lr_size * scale."""
-        p, ptr = self._patches(patches)
+        """The batch of (image id, top, left, fliplr) or (image id, top, left, fliplr, transform) patches as helper/loader.py's
+        load_batch_image builds it, on the device: float32 (x [n, lr_size, lr_size, 1], x2 [n, hr, hr, 1], y_true [n, hr, hr, 1])
+        with hr = lr_size * scale.  With a transform, top and left are coordinates in the transformed image."""
+        p, ptr, aug = self._patches(patches)
         n, lr, hr = len(p), int(lr_size), int(lr_size) * self.scale
         x = np.empty((n, lr, lr, 1), np.float32)
         x2 = np.empty((n, hr, hr, 1), np.float32)
         y = np.empty((n, hr, hr, 1), np.float32)
         fp = ctypes.POINTER(ctypes.c_float)
-        self._check(self._lib.dcscn_train_build_batch(self._h, ptr, n, lr, float(max_value), x.ctypes.data_as(fp), x2.ctypes.data_as(fp),
+        self._check(getattr(self._lib, "dcscn_train_build_batch" + aug)(self._h, ptr, n, lr, float(max_value), x.ctypes.data_as(fp), x2.ctypes.data_as(fp),
                                                       y.ctypes.data_as(fp)))
         return x, x2, y
 
     def train_step_patches(self, patches, lr_size, lr, max_value=255.0, dropout_key=0):
         """train_step on the batch train_build_batch would build, built on the device; returns the stats of train_step."""
-        p, ptr = self._patches(patches)
+        p, ptr, aug = self._patches(patches)
         stats = (ctypes.c_double * 4)()
-        self._check(self._lib.dcscn_train_step_patches(self._h, ptr, len(p), int(lr_size), float(max_value), float(lr),
+        self._check(getattr(self._lib, "dcscn_train_step_patches" + aug)(self._h, ptr, len(p), int(lr_size), float(max_value), float(lr),
                                                        int(dropout_key) & (2 ** 64 - 1), stats))
         return tuple(stats)
 
@@ -654,8 +667,8 @@ class Engine:
 
     def train_local_gradients_patches(self, patches, lr_size, record_ptr, max_value=255.0, dropout_key=0, first_index=0, stream=None):
         """train_local_gradients_device on the shard train_build_batch would build from ``patches``, built on the device."""
-        p, ptr = self._patches(patches)
-        self._check(self._lib.dcscn_train_local_gradients_patches(
+        p, ptr, aug = self._patches(patches)
+        self._check(getattr(self._lib, "dcscn_train_local_gradients_patches" + aug)(
             self._h, ptr, len(p), int(lr_size), float(max_value), int(dropout_key) & (2 ** 64 - 1), int(first_index),
             ctypes.c_void_p(record_ptr), ctypes.c_void_p(stream) if stream else None))
 

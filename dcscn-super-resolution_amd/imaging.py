@@ -295,6 +295,23 @@ def flip(image, flip_type, invert=False):
     return None
 
 
+# The copies augmentation.py writes of every training image, in its order: file <stem><suffix><ext> holds augment(image, code),
+# and --augment_level N writes codes 0 .. N-1 (include/dcscn.h DCSCN_AUG_*: the same codes on the device)
+AUGMENT_SUFFIXES = ("", "_v", "_h", "_hv", "_r1", "_r2", "_r1_v", "_r2_v")
+
+
+def augment(image, transform):
+    """Variant ``transform`` (0 .. 7) of an image [H, W, ...] as a numpy view: [H, W] for 0 .. 3, [W, H] for 4 .. 7."""
+    if transform not in range(len(AUGMENT_SUFFIXES)):
+        raise ValueError("transform %r is not one of 0 .. %d" % (transform, len(AUGMENT_SUFFIXES) - 1))
+    if transform >= 4:
+        image = np.rot90(image, 1 if transform in (4, 6) else -1)
+        return np.flipud(image) if transform >= 6 else image
+    if transform & 2:
+        image = np.fliplr(image)
+    return np.flipud(image) if transform & 1 else image
+
+
 # ---- metrics ------------------------------------------------------------------------------------
 
 def trim_image_as_file(image):

@@ -141,6 +141,8 @@ class SuperResolution:
         self.train_split16 = bool(getattr(flags, "train_split16", False))
         # extension: ... and their weight gradients (engine option "train_split16_wgrad"), independently
         self.train_split16_wgrad = bool(getattr(flags, "train_split16_wgrad", False))
+        # extension: train on the dataset augmentation.py --augment_level N would write, without its files (helper/loader.py)
+        self.train_augment_level = int(getattr(flags, "train_augment_level", 0))
 
         # training parameters (DCSCN.py:50-93)
         fget = lambda k, d: getattr(flags, k, d)
@@ -436,7 +438,7 @@ class SuperResolution:
         """Opens an image directory as a dataset; patches are cut when build_input_batch() is called."""
         from helper import loader
         self.train = loader.DynamicDataSets(self.scale, batch_image_size, channels=self.channels,
-                                            resampling_method=self.resampling_method)
+                                            resampling_method=self.resampling_method, augment_level=self.train_augment_level)
         self.train.set_data_dir(data_dir)
 
     def load_datasets(self, data_dir, batch_dir, batch_image_size, stride_size=0):
@@ -543,11 +545,11 @@ class SuperResolution:
             if self._data_parallel():      # every rank drew the whole batch; it uploads and cuts only its own shard
                 begin, end = shard.train_shard(len(patches), self.train_group.rank, self.train_group.world)
             descriptors = []
-            for filename, top, left, fliplr in patches[begin:end]:
-                image_id = self._device_images.get(filename)
+            for filename, *fields in patches[begin:end]:       # (top, left, fliplr), with train_augment_level >= 2 also the transform
+                image_id = self._device_images.get(filename)    # one upload per base file: a variant is an index map over it
                 if image_id is None:
                     image_id = self._device_images[filename] = eng.train_add_image(self.train.image(filename))
-                descriptors.append((image_id, top, left, fliplr))
+                descriptors.append((image_id, *fields))
             if self._data_parallel():
                 image_loss, mse, _, _ = self._train_shard_step(eng, descriptors, begin)
             else:

@@ -100,6 +100,9 @@ _TABLE = [
     (_B, "train_split16_wgrad", False, "training at f32 accuracy with the weight gradients of layers with min(cin, cout) >= 16 as three scaled f16 products"),
     # ---- extension (not a reference flag): write the reference's TensorBoard log under <tf_log_dir>/train, summaries reduced on the device (dcscn_train_log_pass, include/dcscn.h)
     (_B, "tensorboard", False, "write the TensorBoard event file of the reference's training log once per epoch (needs enable_log)"),
+    # ---- extension (not a reference flag): train on the copies augmentation.py --augment_level N would write of --dataset, cut from the one uploaded
+    # image per file (dcscn_patch_aug, include/dcscn.h).  Not "augment_level": augmentation.py defines that flag itself, with another default
+    (_I, "train_augment_level", 0, "train on the flipped / rotated copies augmentation.py --augment_level N would write, without writing them: 0 .. 8 (0 and 1: the images as they are)"),
     # ---- frozen graphs (args.py:97-98): weights from the Const nodes of a frozen GraphDef (dcscn-super-resolution_amd/frozen.py)
     (_B, "frozenInference", False, "Flag for whether the model to evaluate is frozen."),
     (_S, "frozen_graph_path", "./model_to_freeze/frozen_model_optimized.pb", "the path to a frozen model if performing inference from it"),

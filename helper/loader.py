@@ -32,14 +32,21 @@ class DynamicDataSets:
     """Random patches of the images of a directory (loader.py:278-355), with the reference's sequence of ``random``
     calls: a shuffled image order (random.sample), a crop of batch_image_size * scale (randrange per axis), fliplr with
     probability 1/2 (randrange(2)), then the LR and bicubic images by util.resize_image_by_pil.  Decoded images are
-    cached in memory.  next_patch() draws a patch's descriptor only; load_batch_image() cuts it on the host."""
+    cached in memory.  next_patch() draws a patch's descriptor only; load_batch_image() cuts it on the host.
 
-    def __init__(self, scale, batch_image_size, channels=1, resampling_method="bicubic"):
+    ``augment_level`` N >= 2 trains on the dataset augmentation.py --augment_level N would write of this directory, without the
+    copies: the dataset's entries are (filename, code) -- every file of ``filenames`` in order, and within a file the codes
+    0 .. N-1 of util.AUGMENT_SUFFIXES -- and an entry's image is util.augment of the one cached decode.  The draws are those of an
+    on-disk dataset whose files are listed in that order.  With level 0 or 1 nothing changes."""
+
+    def __init__(self, scale, batch_image_size, channels=1, resampling_method="bicubic", augment_level=0):
         self.scale = scale
         self.batch_image_size = batch_image_size
         self.channels = channels
         self.resampling_method = resampling_method
+        self.augment_level = augment_level
         self.filenames = []
+        self.entries = None                 # augment_level >= 2: [(filename, code)], derived from filenames by init_batch_index
         self.count = 0
         self.batch_index = None
         self.index = 0
@@ -53,6 +60,9 @@ class DynamicDataSets:
             exit(-1)
 
     def init_batch_index(self):
+        if self.augment_level >= 2:         # from the filenames of now: train.py replaces them with rank 0's after set_data_dir
+            self.entries = [(f, code) for f in self.filenames for code in range(self.augment_level)]
+            self.count = len(self.entries)
         self.batch_index = random.sample(range(0, self.count), self.count)
         self.index = 0
 
@@ -66,30 +76,35 @@ class DynamicDataSets:
     def next_patch(self):
         """(filename, top, left, fliplr) of the next patch: the image of the shuffled order (skipping images smaller than a
         patch), a crop of batch_image_size * scale pixels at (top, left), then fliplr with probability 1/2 -- the reference's
-        sequence of random calls, which load_batch_image cuts on the host and SuperResolution.train_batch on the device."""
+        sequence of random calls, which load_batch_image cuts on the host and SuperResolution.train_batch on the device.
+        With augment_level >= 2: (filename, top, left, fliplr, code), top and left in util.augment(image, code)."""
         size = self.batch_image_size * self.scale
         while True:
-            filename = self.filenames[self.get_next_image_no()]
-            height, width = self.image(filename).shape[0:2]
+            image_no = self.get_next_image_no()
+            filename, code = self.entries[image_no] if self.augment_level >= 2 else (self.filenames[image_no], 0)
+            height, width = self.image(filename, code).shape[0:2]
             if height >= size and width >= size:
                 break
             print("Error: %s should have more than %d x %d size." % (filename, size, size))
         top = 0 if height == size else random.randrange(height - size)
         left = 0 if width == size else random.randrange(width - size)
-        return filename, top, left, int(random.randrange(2) == 0)
+        fliplr = int(random.randrange(2) == 0)
+        if self.augment_level >= 2:
+            return filename, top, left, fliplr, code
+        return filename, top, left, fliplr
 
-    def image(self, filename):
-        """The decoded image (uint8 [H, W, 1 | 3]), cached."""
+    def image(self, filename, code=0):
+        """The decoded image (uint8 [H, W, 1 | 3]), cached; ``code``: its variant util.augment(image, code), a view of it."""
         image = self._cache.get(filename)
         if image is None:
             image = util.load_image(filename, print_console=False)
             self._cache[filename] = image
-        return image
+        return util.augment(image, code) if code else image
 
     def load_batch_image(self, max_value):
-        filename, top, left, fliplr = self.next_patch()
+        filename, top, left, fliplr, code = (self.next_patch() + (0,))[:5]
         size = self.batch_image_size * self.scale
-        image = self.image(filename)[top:top + size, left:left + size, :]
+        image = self.image(filename, code)[top:top + size, left:left + size, :]
         image = build_input_image(image, channels=self.channels, convert_ycbcr=True)
         if fliplr:
             image = np.fliplr(image)

@@ -18,6 +18,7 @@
  *   build_optimizer                         (DCSCN.py:379-413)      dcscn_train_begin
  *   sess.run(training_optimizer, ...)       (DCSCN.py:727-769)      dcscn_train_step / dcscn_train_step_device
  *   DynamicDataSets.load_batch_image        (loader.py:278-355)     dcscn_train_add_image + dcscn_train_step_patches
+ *   the same on augmentation.py's copies    (augmentation.py:36-70) dcscn_train_step_patches_aug (dcscn_patch_aug.transform)
  *   Saver.save / restore of the slots       (tf_graph.py:251-280)   dcscn_get_tensor / dcscn_set_train_tensor
  *
  * Conventions: plain C types only; all image tensors are dense NHWC float32 with C == 1
@@ -577,6 +578,33 @@ int dcscn_train_build_batch(dcscn_handle h, const dcscn_patch* patches, int n, i
  * crosses PCIe.  Synchronises only when stats != NULL (the 4 doubles of dcscn_train_step). */
 int dcscn_train_step_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value, double lr,
                              uint64_t dropout_key, double* stats);
+/* The 8-fold augmented dataset (augmentation.py: flipped and rotated copies of every image, files <stem><suffix><ext>) without
+ * the copies: a patch names the variant of its image as an index map over the one uploaded image.  For a stored image in [H, W]
+ * the variant out is [H, W] for codes 0 .. 3 and [W, H] for codes 4 .. 7 (numpy is the specification):
+ *   code  suffix   numpy                      out[i, j]
+ *   0     ""       m                          in[i, j]
+ *   1     "_v"     flipud(m)                  in[H-1-i, j]
+ *   2     "_h"     fliplr(m)                  in[i, W-1-j]
+ *   3     "_hv"    flipud(fliplr(m))          in[H-1-i, W-1-j]
+ *   4     "_r1"    rot90(m)                   in[j, W-1-i]
+ *   5     "_r2"    rot90(m, -1)               in[H-1-j, i]
+ *   6     "_r1_v"  flipud(rot90(m))           in[j, i]
+ *   7     "_r2_v"  flipud(rot90(m, -1))       in[H-1-j, W-1-i]
+ * augmentation.py --augment_level N writes codes 0 .. N-1.  top and left are coordinates in the VARIANT (so the crop must lie inside
+ * [W, H] for codes 4 .. 7), and fliplr mirrors the crop afterwards, as the loader's random flip does:
+ *   patch = fliplr?( variant(image)[top : top + HR, left : left + HR] )
+ * and from there everything is dcscn_patch's pipeline, bit for bit what the host loader cuts from the file augmentation.py writes
+ * (for a lossless format; a JPEG copy is re-encoded, the variant here is cut from the original decode).  The three calls have the
+ * semantics of their namesakes, which are their transform = 0 case; a transform outside 0 .. 7 is DCSCN_ERR_INVALID_ARG. */
+enum { DCSCN_AUG_NONE = 0, DCSCN_AUG_V = 1, DCSCN_AUG_H = 2, DCSCN_AUG_HV = 3, DCSCN_AUG_R1 = 4, DCSCN_AUG_R2 = 5, DCSCN_AUG_R1_V = 6,
+       DCSCN_AUG_R2_V = 7, DCSCN_AUG_COUNT = 8 };
+typedef struct dcscn_patch_aug {
+    int32_t image, top, left, fliplr, transform;
+} dcscn_patch_aug;
+int dcscn_train_build_batch_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value, float* x, float* x2,
+                                float* y_true);
+int dcscn_train_step_patches_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value, double lr,
+                                 uint64_t dropout_key, double* stats);
 /* Data-parallel training: every rank holds a full replica (variables, slots, beta powers) on its own handle.  Per step each
  * rank computes the gradient of its shard of the global batch into a RECORD, the ranks exchange the records (any all-gather:
  * the library does not communicate), and every rank reduces all records in rank order and applies the same update -- the
@@ -603,6 +631,9 @@ int dcscn_train_local_gradients_device(dcscn_handle h, const float* x, const flo
 /* The same with the shard built on the device from dcscn_patch descriptors, as dcscn_train_step_patches builds its batch. */
 int dcscn_train_local_gradients_patches(dcscn_handle h, const dcscn_patch* patches, int n, int lr_size, double max_value,
                                         uint64_t dropout_key, int64_t first_index, float* record_out, void* stream);
+/* The same from dcscn_patch_aug descriptors (above). */
+int dcscn_train_local_gradients_patches_aug(dcscn_handle h, const dcscn_patch_aug* patches, int n, int lr_size, double max_value,
+                                            uint64_t dropout_key, int64_t first_index, float* record_out, void* stream);
 int dcscn_train_apply_records(dcscn_handle h, const float* records, int world, double lr, double* stats, void* stream);
 /* Read a variable (any time after its dcscn_set_tensor; the trained value while training), a gradient or a slot: `count`
  * must equal its number of values. */

@@ -43,6 +43,12 @@ defaults with pixel_shuffler = false (its README's training command line), L7_x2
 list times one handle per name, alternating step by step in ONE process, and prints one JSON line with every median.
 
     python tools/train_bench.py --optimizer adam,adagrad,adadelta,rmsprop
+
+--augment times the device-batch loop of --loop at --train_augment_level 0 and 8 (helper/loader.py: the eight flipped / rotated variants of
+every image, cut from the one uploaded image by batch_gather's index map) on two models of one process, alternating step by step, for
+c-DCSCN x2 at 20 x 48^2: one JSON line with both medians and their ratio.
+
+    python tools/train_bench.py --augment
 """
 import argparse
 import json
@@ -346,11 +352,11 @@ def bench_separable(name, n, size, steps, warmup):
                 min_ms=[round(float(np.min(times[0])), 4), round(float(np.min(times[1])), 4)])
 
 
-def loop_model(name, n, size, tmp):
+def loop_model(name, n, size, tmp, augment_level=0):
     from dcscn_amd.model import SuperResolution
     from helper import args
     f = {k: args.FLAGS._flags[k].default for k in args.FLAGS}
-    f.update(CONFIGS[name], self_ensemble=1, batch_num=n, batch_image_size=size, checkpoint_dir=tmp, log_filename="", **flags())
+    f.update(CONFIGS[name], self_ensemble=1, batch_num=n, batch_image_size=size, checkpoint_dir=tmp, log_filename="", train_augment_level=augment_level, **flags())
     m = SuperResolution(type("Flags", (dict,), {"__getattr__": dict.__getitem__})(f))
     m.build_graph()
     m.build_optimizer()
@@ -396,6 +402,30 @@ def bench_loop(name, n, size, steps, warmup, device_only):
     return out
 
 
+def bench_augment(name, n, size, steps, warmup, levels=(0, 8)):
+    """build_input_batch() + train_batch() at every train_augment_level of `levels`, one model each, alternating step by step."""
+    import random
+    import tempfile
+    import time
+    random.seed(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        models = [loop_model(name, n, size, os.path.join(tmp, str(level)), level) for level in levels]
+        times = [[] for _ in levels]
+        for i in range(warmup + steps):
+            for k, m in enumerate(models):
+                t0 = time.perf_counter()
+                m.build_input_batch()
+                m.train_batch()                   # returns after the step's stats are on the host
+                if i >= warmup:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+        uploads = [len(m._device_images) for m in models]
+        for m in models:
+            m.close()
+    med = [float(np.median(t)) for t in times]
+    return dict(augment_compare=name, batch=n, lr_size=size, steps=steps, warmup=warmup, levels=list(levels), ms=[round(v, 4) for v in med],
+                min_ms=[round(float(np.min(t)), 4) for t in times], ratio_to_first=[round(v / med[0], 4) for v in med], uploaded_images=uploads)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="L7_x2", choices=sorted(CONFIGS))
@@ -416,6 +446,7 @@ def main():
     ap.add_argument("--transposed", action="store_true", help="time the transposed-conv nets' HIP step and torch step alternating in one process")
     ap.add_argument("--optimizer", default="adam",
                     help="--optimizer of the timed handle; a comma-separated list times one handle each, alternating in one process")
+    ap.add_argument("--augment", action="store_true", help="time the device-batch loop at train_augment_level 0 and 8 alternating in one process (c-DCSCN x2)")
     ap.add_argument("--library", help="load this libdcscn_hip.so instead of the tree's (e.g. one built from the parent commit)")
     a = ap.parse_args()
     if a.library:
@@ -435,6 +466,9 @@ def main():
     if a.separable or a.transposed:
         for name, n, size in (SEPARABLE_CASES if a.separable else TRANSPOSED_CASES):
             print(json.dumps(bench_separable(name, n, size, a.steps, a.warmup)), flush=True)
+        return
+    if a.augment:
+        print(json.dumps(bench_augment("L7_x2", a.batch, a.size, a.steps, a.warmup)), flush=True)
         return
     if a.loop:
         for name, n, size in LOOP_CASES:

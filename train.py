@@ -34,6 +34,10 @@ def main(not_parsed_args):
     if FLAGS.build_batch:
         print("Error. --build_batch true (BatchDataSets) is not supported; use --build_batch false.")
         sys.exit(-1)
+    if not 0 <= FLAGS.train_augment_level <= 8:
+        print("Error. --train_augment_level %d is not one of 0 .. 8 (augmentation.py's levels; 0 and 1 train on the images as they are)."
+              % FLAGS.train_augment_level)
+        sys.exit(-1)
 
     refusal = shard.train_batch_refusal(FLAGS.batch_num, int(os.environ.get("WORLD_SIZE", "1")))
     if refusal:                                             # before the process group exists: every rank leaves the same way
